@@ -29,7 +29,7 @@ extern "C" {
 #define ZJNI_BLOCKSIZE_MAX (1u << 17)  /* ZSTD_BLOCKSIZE_MAX, N/zstd.h:147-148: inputs up to here become single-block frames */
 #define ZJNI_FRAME_MAX (2u << 20)      /* largest input the compress entries take: multi-block frames (N/compress/zstd_compress.c:4591-4692),
                                         * byte-identical to ZSTD_compress2 with the level's own parameters, as long as the frame fits the level's
-                                        * window — 512 KiB / 1 MiB / 2 MiB at levels 1 / 2 / 3; beyond that ZJNI_ERROR_unsupported */
+                                        * window — 512 KiB / 1 MiB / 2 MiB at levels 1 / 2 / 3, 512 KiB at negative levels; beyond that ZJNI_ERROR_unsupported */
 #define ZJNI_LEVEL4_MAX (1u << 17)     /* level 4 (N/compress/clevels.h:84,110): greedy on the hash chain up to 16 KiB (ZSTD_compressBlock_greedy,
                                         * N/compress/zstd_lazy.c:1784), double-fast with 2^17-entry tables up to here; larger inputs run the
                                         * reference's row-based match finder, which this library does not restate: ZJNI_ERROR_unsupported */
@@ -76,7 +76,10 @@ size_t zjni_decompress_batch_device(const void* d_src, const uint64_t* d_src_off
 /* Replaces ZSTD_CCtx_reset + ZSTD_compress2 (N/jni_fast_zstd.c:606-607, :633-635) for n buffers at
  * once: each buffer becomes one standard zstd frame (content size in the header, no checksum,
  * no dictID) that any zstd decoder accepts.  level: 1..3 (N/compress/clevels.h), or 4 for inputs up to ZJNI_LEVEL4_MAX / 5..8 up to ZJNI_LAZY_MAX (plain
- * entries only: no dictionary, no explicit table sizes; a wave-per-frame kernel with one lane parsing — exact, not fast).  Buffers larger than
+ * entries only: no dictionary, no explicit table sizes; a wave-per-frame kernel with one lane parsing — exact, not fast).  Negative levels (zstd's
+ * --fast=N, down to ZSTD_minCLevel() = -131072; lower ones are clamped to it, as the reference clamps them): the fast strategy with the parameters of
+ * row 0 of the size's table, the match loop stepping N + 1 and raw literals, on level 1's routes (every entry that takes a level, the blocking
+ * ones, the aggregator, begin/finish and the multi-device entry included; no dictionary, no explicit table sizes, no streams).  Buffers larger than
  * ZJNI_BLOCKSIZE_MAX become multi-block frames (one wavefront per frame, block after block; see ZJNI_FRAME_MAX for the
  * range); beyond it d_result[i] reports ZJNI_ERROR_unsupported and the buffer stays on the CPU path.
  * Destination capacity (d_dst_off[i+1] - d_dst_off[i]): with zjni_compressBound(srcSize) a frame always fits.  With less, the answer is
@@ -119,7 +122,7 @@ size_t zjni_decompress_usingDDict(void* dst, size_t dstCapacity, const void* src
  * (double-fast): hashLog 6..17, chainLog 6..16, frames byte-identical to the reference called with the same two
  * parameters.  Not set, level 3 uses the reference's own sizes for the input (16 / 15 at 64 KiB: the frames of a plain
  * Zstd.compress(x, 3)); 14 / 13 are the sizes the LDS-resident finders of small batches are built for, honoured when asked for.
- * Other levels with a non-zero value: ZSTD_error_parameter_unsupported; out of range: parameter_outOfBound. */
+ * Other levels with a non-zero value (negative levels included): ZSTD_error_parameter_unsupported; out of range: parameter_outOfBound. */
 /* Frame-header parameters: the `checksum` argument of the *_advanced and *_usingCDict entries is a flag word —
  * ZSTD_c_checksumFlag, ZSTD_c_contentSizeFlag = 0 (ZstdCompressCtx.setContentSize0(false), N/jni_fast_zstd.c:301-308: no frame
  * content size, a window descriptor instead; without a dictionary only) and ZSTD_c_dictIDFlag = 0 (setDictID0(false), :313-320).
@@ -292,16 +295,16 @@ int zjni_last_timing2(float* out8);
 /* Which match finder served list A of the last large compress call on this device (bench.py names the roofline's kernel from this, not from the
  * environment: a refused LDS attribute, a scratch budget or a failed allocation changes the route silently).  Negative: no device. */
 #define ZJNI_ROUTE_NONE 0         /* no large-batch compress call yet */
-#define ZJNI_ROUTE_FUSED 1        /* zj_encode_kernel alone (small batches, levels 1-2) */
+#define ZJNI_ROUTE_FUSED 1        /* zj_encode_kernel alone (small batches, levels 1-2 and negative levels) */
 #define ZJNI_ROUTE_WAVE 2         /* zj_enc_match_wave_kernel (small level-3 batches, tables in LDS) */
-#define ZJNI_ROUTE_LANE 3         /* zj_enc_match_kernel (levels 1-2; level 3 under ZJNI_LANE_MACHINE=0 without flags) */
+#define ZJNI_ROUTE_LANE 3         /* zj_enc_match_kernel (levels 1-2; level 3 under ZJNI_LANE_MACHINE=0 without flags); negative levels: the same machine in zj_enc_match_kernel_neg */
 #define ZJNI_ROUTE_LANE_GATED 4   /* zj_enc_match_gated_kernel (ZJNI_LANE_MACHINE=0 with flags) */
 #define ZJNI_ROUTE_RUN 5          /* zj_enc_match_run_kernel without need flags */
 #define ZJNI_ROUTE_RUN_FLAGS 6    /* zj_enc_match_run_kernel behind zj_enc_worth_kernel / zj_enc_need_kernel */
 #define ZJNI_ROUTE_HYBRID 7       /* ZJNI_HYBRID=1: lane and wave kernels side by side */
 #define ZJNI_ROUTE_OTHER 8        /* levels 4-8, dictionaries, multi-block only */
 #define ZJNI_ROUTE_WAVE_HBM 9     /* zj_encode_multi_kernel: level-3 frames of batches below ZJNI_L3_WAVE_MAX, wave per frame over HBM tables (zj_match_wavex.h) */
-#define ZJNI_ROUTE_WIDE 10        /* zj_enc_match_wide_kernel: the launch of frames above 64 KiB (list B); never zjni_last_route()'s answer — see zjni_last_lists */
+#define ZJNI_ROUTE_WIDE 10        /* zj_enc_match_wide_kernel: the launch of frames above 64 KiB (list B; negative levels: zj_enc_match_wide_kernel_neg); never zjni_last_route()'s answer — see zjni_last_lists */
 #define ZJNI_ROUTE_PIPE 11        /* zj_encode_pipe_kernel (round 6): multi-block frames of a batch that leaves wave slots empty, a parse wave a block ahead of an entropy wave per frame;
                                      decided on the device from the list counts, so zjni_last_route() says it only after zjni_last_lists() has read them */
 int zjni_last_route(void);

@@ -28,8 +28,8 @@ def upload(arr):
 soff = upload(np.arange(n + 1, dtype=np.uint64) * size); coff = upload(np.arange(n + 1, dtype=np.uint64) * bound)
 csz = dmalloc(n * 8); dsz = dmalloc(n * 8); poff = dmalloc((n + 1) * 8)
 if os.environ.get("PROF_DATA") == "xml":          # bench.py --config 1's buffers: overlapping slices of the reference's xml fixture
-    from oracle import ref
-    xml = np.frombuffer(ref.decompress(open(os.path.join(ROOT, "tests", "golden", "xml-1.zst"), "rb").read(), 6_000_000), dtype=np.uint8)
+    from oracle import port           # the plain-C decoder (zso_* symbols): unaffected by a system libzstd the profiler loads into the process
+    xml = np.frombuffer(port.decompress(open(os.path.join(ROOT, "tests", "golden", "xml-1.zst"), "rb").read(), 6_000_000), dtype=np.uint8)
     host = np.empty(n * size, dtype=np.uint8); span = xml.size - size
     for i in range(n):
         o = (i * 4099) % span; host[i * size:(i + 1) * size] = xml[o:o + size]

@@ -134,15 +134,24 @@ ZJ_HD void ze_adjust(u32& windowLog, u32& chainLog, u32& hashLog, u32 srcSize) {
     if (chainLog > windowLog) chainLog = windowLog;
     if (windowLog < 10) windowLog = 10;
 }
-struct ZEParams { u32 windowLog, chainLog, hashLog, minMatch, strategy, searchLog; };      // (window logs > 14 at strategies 3-5: the row-based finder, ze_params_uses_rows)      // strategy (ZSTD_strategy): 1 fast, 2 double-fast, 3 greedy, 4 lazy, 5 lazy2 (3-5 on the hash chain), 0 = not served
+struct ZEParams { u32 windowLog, chainLog, hashLog, minMatch, strategy, searchLog, targetLength; };      // (window logs > 14 at strategies 3-5: the row-based finder, ze_params_uses_rows)      // strategy (ZSTD_strategy): 1 fast, 2 double-fast, 3 greedy, 4 lazy, 5 lazy2 (3-5 on the hash chain), 0 = not served
 // "level" arguments are level words: the level in the low byte, then ZstdCompressCtx.setHashLog / setChainLog
 // (ZSTD_c_hashLog / ZSTD_c_chainLog, 0 = not set) — honoured for the double-fast strategy, whose tables live in HBM on
 // the lane-per-frame path and can therefore have the level's own sizes (16 / 15 at level 3) or any other.
 #define ZE_LW(level, hashLog, chainLog) ((u32)(level) | ((u32)(hashLog) << 8) | ((u32)(chainLog) << 16))
 #define ZE_LW_LEVEL(lw) ((lw) & 0xFFu)
-#define ZE_LW_HL(lw) (((lw) >> 8) & 0xFFu)
-#define ZE_LW_CL(lw) (((lw) >> 16) & 0xFFu)
-#define ZE_LW_PERIOD(lw) (((lw) >> 24) & 0xFu)    /* match kernel only: rotation period of the double-fast lane machine, 0 = default */
+// Negative levels (zstd's --fast=N): the word holds level 1 in the low byte (the fast strategy: every dispatch on the level treats the frame as
+// level 1's), ZE_LW_NEG, and the acceleration N (ZSTD_c_targetLength = -level) in bits 8-24 where a positive level keeps hashLog, chainLog and
+// the period — none of which a negative level takes, so they read as 0.  The acceleration is carried clamped to ZE_ACCEL_CAP: the fast loop
+// starts a search only while ip0 + (N + 1) + 1 < blockEnd - 8, and with N + 1 >= ZE_BLOCK_MAX no block ever starts one, so every larger N
+// (up to the reference's ZSTD_TARGETLENGTH_MAX = 131072) makes the same frame (tests/test_emu_negative_levels.py checks it against the reference).
+#define ZE_LW_NEG (1u << 30)
+#define ZE_ACCEL_CAP (ZE_BLOCK_MAX - 1u)
+#define ZE_LW_ACCEL(lw) (((lw) & ZE_LW_NEG) ? (((lw) >> 8) & 0x1FFFFu) : 0u)
+#define ZE_LW_NEGATIVE(accel) (1u | (((accel) < ZE_ACCEL_CAP ? (u32)(accel) : ZE_ACCEL_CAP) << 8) | ZE_LW_NEG)
+#define ZE_LW_HL(lw) (((lw) & ZE_LW_NEG) ? 0u : ((lw) >> 8) & 0xFFu)
+#define ZE_LW_CL(lw) (((lw) & ZE_LW_NEG) ? 0u : ((lw) >> 16) & 0xFFu)
+#define ZE_LW_PERIOD(lw) (((lw) & ZE_LW_NEG) ? 0u : ((lw) >> 24) & 0xFu)    /* match kernel only: rotation period of the double-fast lane machine, 0 = default */
 #define ZE_LW_WAVE_ROUTE (1u << 29)              /* classification only: every single-block frame of the call goes to the wave-per-frame kernel (level 3, batches too small to fill the lane pipeline) */
 #define ZE_LW_IMPLICIT (1u << 28)                /* hashLog / chainLog in the word are the level's OWN (16 / 15 at level 3: what a caller who set nothing gets) — multi-block frames, whose blocks take the level's parameters of their size, accept such a word */
 // "tuned": table sizes the LDS-resident finders (fused kernel, wave-per-frame matcher) cannot hold — everything but the LDS-sized pair itself
@@ -152,10 +161,21 @@ struct ZEParams { u32 windowLog, chainLog, hashLog, minMatch, strategy, searchLo
 ZJ_HD ZEParams ze_params_of(u32 levelWord, u32 srcSize) {
     u32 const level = ZE_LW_LEVEL(levelWord), hl = ZE_LW_HL(levelWord), cl = ZE_LW_CL(levelWord);
     u32 w, c, h, mm, st;
+    if (levelWord & ZE_LW_NEG) {
+        // negative levels: row 0 of the size's table ("base for negative levels", clevels.h:28,54,80,106) with targetLength = the
+        // acceleration (zstd_compress.c:7768-7777), then ZSTD_adjustCParams_internal
+        if (srcSize <= (16u << 10)) { w = 14; c = 12; h = 13; mm = 5; }
+        else if (srcSize <= (128u << 10)) { w = 17; c = 12; h = 12; mm = 5; }
+        else if (srcSize <= (256u << 10)) { w = 18; c = 12; h = 13; mm = 5; }
+        else { w = 19; c = 12; h = 13; mm = 6; }
+        ze_adjust(w, c, h, srcSize);
+        ZEParams q; q.windowLog = w; q.chainLog = c; q.hashLog = h; q.minMatch = mm; q.strategy = 1; q.searchLog = 1; q.targetLength = ZE_LW_ACCEL(levelWord);
+        return q;
+    }
     if (level >= 5 && level <= 8) {
         // clevels.h:111-114, inputs <= 16 KiB: lazy (level 5) and lazy2 (levels 6-8) on the hash chain — the window log stays <= 14, so the
         // reference does not switch to its row-based finder; larger inputs at these levels do, and are not served (strategy 0)
-        ZEParams q; q.windowLog = q.chainLog = q.hashLog = q.minMatch = q.strategy = q.searchLog = 0;
+        ZEParams q; q.windowLog = q.chainLog = q.hashLog = q.minMatch = q.strategy = q.searchLog = q.targetLength = 0;
         if (srcSize > (128u << 10)) return q;
         if (srcSize <= (16u << 10)) {
             w = 14; c = 14; h = 14;
@@ -174,7 +194,7 @@ ZJ_HD ZEParams ze_params_of(u32 levelWord, u32 srcSize) {
         // clevels.h:84 / :110.  <= 16 KiB: greedy on the hash chain (the window log stays <= 14, where the reference does not switch to its
         // row-based match finder, zstd_compress.c:238-245); <= 128 KiB: double-fast with 2^17-entry tables; beyond: greedy on the row
         // finder — not served (strategy 0)
-        ZEParams q; q.searchLog = 0;
+        ZEParams q; q.searchLog = 0; q.targetLength = 0;
         if (srcSize <= (16u << 10)) { w = 14; c = 14; h = 14; mm = 4; st = 3; q.searchLog = 4; }
         else if (srcSize <= (128u << 10)) { w = 17; c = 17; h = 17; mm = 4; st = 2; q.searchLog = 2; }
         else { q.windowLog = q.chainLog = q.hashLog = q.minMatch = q.strategy = 0; return q; }
@@ -198,7 +218,7 @@ ZJ_HD ZEParams ze_params_of(u32 levelWord, u32 srcSize) {
     }
     ze_adjust(w, c, h, srcSize);
     if (srcSize > (128u << 10)) {                             // multi-block frames run the level's own table sizes (tables in HBM)
-        ZEParams q; q.windowLog = w; q.chainLog = c; q.hashLog = h; q.minMatch = mm; q.strategy = st; q.searchLog = 1;
+        ZEParams q; q.windowLog = w; q.chainLog = c; q.hashLog = h; q.minMatch = mm; q.strategy = st; q.searchLog = 1; q.targetLength = 0;
         return q;
     }
     if (st == 2 && (hl | cl)) {   // explicit ZSTD_c_hashLog / ZSTD_c_chainLog: override, then ZSTD_adjustCParams_internal again (zstd_compress.c:1640-1655)
@@ -208,9 +228,11 @@ ZJ_HD ZEParams ze_params_of(u32 levelWord, u32 srcSize) {
     } else if (st == 2) {     // LDS budget: ZSTD_c_hashLog = 14, ZSTD_c_chainLog = 13, then adjust again
         if (h > ZE_L3_HASHLOG || c > ZE_L3_CHAINLOG) { if (h > ZE_L3_HASHLOG) h = ZE_L3_HASHLOG; if (c > ZE_L3_CHAINLOG) c = ZE_L3_CHAINLOG; ze_adjust(w, c, h, srcSize); }
     }
-    ZEParams p; p.windowLog = w; p.chainLog = c; p.hashLog = h; p.minMatch = mm; p.strategy = st; p.searchLog = 1;
+    ZEParams p; p.windowLog = w; p.chainLog = c; p.hashLog = h; p.minMatch = mm; p.strategy = st; p.searchLog = 1; p.targetLength = 0;
     return p;
 }
+// the fast loop's stepSize (zstd_fast.c:200): targetLength + !targetLength + 1 — 2 at levels 1-2, the acceleration + 1 at negative levels
+ZJ_HD u32 ze_fast_step(u32 levelWord) { u32 const a = ZE_LW_ACCEL(levelWord); return a + (a == 0u ? 1u : 0u) + 1u; }
 // ZSTD_resolveRowMatchFinderMode (zstd_compress.c:238-245): greedy / lazy / lazy2 search rows of tagged entries instead of the hash
 // chain once the window log exceeds 14
 ZJ_HD bool ze_params_uses_rows(const ZEParams& p) { return p.strategy >= 3u && p.strategy <= 5u && p.windowLog > 14u; }
@@ -289,14 +311,14 @@ ZJ_DEV u32 ze_tag8(u64 w) { return (u32)((w * 0x9E3779B97F4A7C15ull) >> 49); }  
 // it moves from ip2/ip3 to ip0/ip1.  The second table write of an iteration (table[hash1] = ip1) happens
 // on every path of the reference, so it is done up front, right after table[hash1] has been read.
 template <class E>
-ZJ_DEV u32 ze_block_fast(ZEOut& o, const u8* src, u32 srcSize, u32 hlog, u32 mls, typename E::T* table) {
+ZJ_DEV u32 ze_block_fast(ZEOut& o, const u8* src, u32 srcSize, u32 hlog, u32 mls, typename E::T* table, u32 stepSize = 2u) {
     const u8* const istart = src; const u8* const iend = src + srcSize; const u8* const ilimit = iend - 8;
     const u8* anchor = istart; const u8* ip0 = istart + 1; const u8* ip1; const u8* ip2; const u8* ip3;
     u32 rep1 = 1, rep2 = 0;                       // rep {1,4}: 4 > maxRep == 1 at the first position of a frame
     u32 hash0, hash1, matchE, cur0 = 0, offcode = 0, mLength = 0, step;
     const u8* match0 = istart; const u8* nextStep;
     for (;;) {
-        step = 2; nextStep = ip0 + 128;
+        step = stepSize; nextStep = ip0 + 128;
         ip1 = ip0 + 1; ip2 = ip0 + step; ip3 = ip2 + 1;
         if (ip3 >= ilimit) break;
         u64 w0 = ld64(ip0), w1 = ld64(ip1);
@@ -652,7 +674,7 @@ ZJ_DEV u32 ze_block_lazy(ZEOut& o, const u8* src, u32 srcSize, const ZEParams& p
 // zstd_double_fast.c:153-163, :238-246: offsets beyond the data seen so far are parked and restored).  The frame fits its
 // window (checked by the caller), so every earlier position is a legal candidate.
 template <class E>
-ZJ_DEV u32 ze_block_fast_x(ZEOut& o, const u8* base, u32 start, u32 end, u32 hlog, u32 mls, typename E::T* table, const u32* repIn, u32* repOut) {
+ZJ_DEV u32 ze_block_fast_x(ZEOut& o, const u8* base, u32 start, u32 end, u32 hlog, u32 mls, typename E::T* table, const u32* repIn, u32* repOut, u32 stepSize = 2u) {
     const u8* const istart = base + start; const u8* const iend = base + end; const u8* const ilimit = iend - 8;
     const u8* anchor = istart; const u8* ip0 = istart + (start == 0 ? 1 : 0); const u8* ip1; const u8* ip2; const u8* ip3;
     u32 rep1 = repIn[0], rep2 = repIn[1], saved1 = 0, saved2 = 0;
@@ -662,7 +684,7 @@ ZJ_DEV u32 ze_block_fast_x(ZEOut& o, const u8* base, u32 start, u32 end, u32 hlo
     u32 hash0, hash1, matchE, cur0 = 0, offcode = 0, mLength = 0, step;
     const u8* match0 = base; const u8* nextStep;
     for (;;) {
-        step = 2; nextStep = ip0 + 128;
+        step = stepSize; nextStep = ip0 + 128;
         ip1 = ip0 + 1; ip2 = ip0 + step; ip3 = ip2 + 1;
         if (ip3 >= ilimit) break;
         u64 w0 = ld64(ip0), w1 = ld64(ip1);
@@ -1591,7 +1613,7 @@ ZJ_DEV u64 ze_compress_t(const G& g, ZEncShared& sh, u8* lds, const u8* src0, u3
         u32 const strategy = ZJ_UNI(sh.strategy), hlog = ZJ_UNI(sh.hashLog), clog = ZJ_UNI(sh.chainLog), mls = ZJ_UNI(sh.minMatch);
         if (!pre && ba) {                                  // one block of a frame: its tables (HBM, cleared by the caller before block 0) and repcodes carry on
 #if defined(ZJ_TUNING_KERNELS) || !ZJ_ON_GPU          /* ZWaveF: exact, measured slower than the one-lane parse at levels 1-2 (2 048 x 512 KiB: 156 ms against 138) — tuning builds and the emulation only */
-            if (strategy == 1 && ba->serialParse != 1u && !(ba->serialParse & 4u)) {     // levels 1-2: the fast strategy on the whole wave (zj_match_wavex.h, ZWaveF)
+            if (strategy == 1 && ba->serialParse != 1u && !(ba->serialParse & 4u) && !(level & ZE_LW_NEG)) {     // levels 1-2: the fast strategy on the whole wave (zj_match_wavex.h, ZWaveF; step 2 only)
                 ZEOut o; o.seqs = seqs; o.litOff = (u32*)(ws + ZE_WS_BODY); o.n = 0; o.lit = 0;
                 u32 const lastLL = zx_block_fast_wave(lds, o, ba->frameBase, ba->frameSize, ba->start, ba->start + srcSize, hlog, mls, ba->tables, sh.blkRep, sh.blkNextRep, (ba->serialParse & 3u) == 0u);
                 GRP_SERIAL(g) { sh.nbSeq = o.n; sh.litSize = o.lit + lastLL; sh.lastLL = lastLL; }
@@ -1604,7 +1626,7 @@ ZJ_DEV u64 ze_compress_t(const G& g, ZEncShared& sh, u8* lds, const u8* src0, u3
             } else
             GRP_SERIAL(g) {
                 ZEOut o; o.seqs = seqs; o.litOff = (u32*)(ws + ZE_WS_BODY); o.n = 0; o.lit = 0;
-                u32 const lastLL = (strategy == 1) ? ze_block_fast_x<ZEEnt32>(o, ba->frameBase, ba->start, ba->start + srcSize, hlog, mls, ba->tables, sh.blkRep, sh.blkNextRep)
+                u32 const lastLL = (strategy == 1) ? ze_block_fast_x<ZEEnt32>(o, ba->frameBase, ba->start, ba->start + srcSize, hlog, mls, ba->tables, sh.blkRep, sh.blkNextRep, ze_fast_step(level))
                                                    : ze_block_dfast_x<ZEEnt32>(o, ba->frameBase, ba->start, ba->start + srcSize, hlog, clog, mls, ba->tables, ba->tables + (1u << hlog), sh.blkRep, sh.blkNextRep);
                 sh.nbSeq = o.n; sh.litSize = o.lit + lastLL; sh.lastLL = lastLL;
             }
@@ -1641,7 +1663,7 @@ ZJ_DEV u64 ze_compress_t(const G& g, ZEncShared& sh, u8* lds, const u8* src0, u3
                 ZEOut o; o.seqs = seqs; o.litOff = (u32*)(ws + ZE_WS_BODY); o.n = 0; o.lit = 0;
                 TIdx* const t = (TIdx*)lds;
                 typedef typename ZEEntOf<TIdx>::E EntLds;
-                u32 const lastLL = (strategy == 1) ? ze_block_fast<EntLds>(o, src, srcSize, hlog, mls, t)
+                u32 const lastLL = (strategy == 1) ? ze_block_fast<EntLds>(o, src, srcSize, hlog, mls, t, ze_fast_step(level))
                                                    : ze_block_dfast<EntLds>(o, src, srcSize, hlog, clog, mls, t, t + (1u << hlog));
                 sh.nbSeq = o.n; sh.litSize = o.lit + lastLL; sh.lastLL = lastLL;
             }
@@ -1705,6 +1727,7 @@ ZJ_DEV u64 ze_compress_t(const G& g, ZEncShared& sh, u8* lds, const u8* src0, u3
             u32 const seg = (n + 3) / 4;
             u32 mode = 2;                                                      // 0 raw, 1 rle, 2 compressed (new table), 3 compressed (dictionary's table)
             if (n < (hufRep == ZC_REPEAT_VALID ? 6u : 64u)) mode = 0;           // ZSTD_minLiteralsToCompress (strategy <= 6)
+            if (level & ZE_LW_NEG) mode = 0;                                   // negative levels: ZSTD_literalsCompressionIsDisabled (fast strategy, targetLength > 0) -> ZSTD_noCompressLiterals, no histogram, no table
             if (mode == 2) {
                 bool const suspect = (nbSeq == 0) || (n / nbSeq >= 20);
                 GRP_FOR(g, i, 1024) (&e.hist[0][0])[i] = 0;
@@ -2543,7 +2566,7 @@ ZJ_DEV void ze_match_lane_serial(const u8* src, u32 srcSize, u32 level, u8* tabl
         ZEParams const p = ze_params_of(level, srcSize);
         // fast: plain u16 entries (one probe per position; tags cost more in table sectors than they save);
         // double-fast: tagged 4-byte entries (two probes per position, most candidates rejected by tag)
-        if (p.strategy == 1) lastLL = ze_block_fast<ZEEnt16>(o, src, srcSize, p.hashLog, p.minMatch, (u16*)table);
+        if (p.strategy == 1) lastLL = ze_block_fast<ZEEnt16>(o, src, srcSize, p.hashLog, p.minMatch, (u16*)table, ze_fast_step(level));
         else { u32* const t = (u32*)table; lastLL = ze_block_dfast<ZEEntTag>(o, src, srcSize, p.hashLog, p.chainLog, p.minMatch, t, t + (1u << p.hashLog)); }
     }
     meta[0] = o.n; meta[1] = o.lit + lastLL; meta[2] = lastLL;

@@ -468,10 +468,21 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void
                                                            const u32* __restrict__ list, const u32* countPtr, u32* workCounter,
                                                            u8* tables, u32 tableStride, u8* fscratch, u32 maxSrc, u32* meta, u32* doneList, u32* doneCount,
                                                            u32 listBase, u32 sliceLen, unsigned long long* work2) {
+    level &= ~ZE_LW_NEG;                                  // negative levels run zj_enc_match_kernel_neg: here the step is 2 at compile time
     u32 const count = zj_slice_count(countPtr, listBase, sliceLen);
     list += listBase;
     if (ZE_LW_LEVEL(level) == 3) zj_match_run<ZLaneD<ZEEntTag> >(src, srcOff, level, list, count, workCounter, tables, tableStride, fscratch, maxSrc, meta, doneList, doneCount, work2);
     else zj_match_run<ZLaneF<ZEEnt16> >(src, srcOff, level, list, count, workCounter, tables, tableStride, fscratch, maxSrc, meta, doneList, doneCount, work2);
+}
+// Negative levels (zstd's --fast=N; level word with ZE_LW_NEG): the same lane-per-frame fast machine (ZLaneF) with the level's step N + 1 carried in
+// the word.  A kernel of its own so that the level 1-2 kernel above keeps its constant step and its registers (ZJNI_ROUTE_LANE reports both).
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void zj_enc_match_kernel_neg(const u8* __restrict__ src, const u64* __restrict__ srcOff, u32 level,
+                                                           const u32* __restrict__ list, const u32* countPtr, u32* workCounter,
+                                                           u8* tables, u32 tableStride, u8* fscratch, u32 maxSrc, u32* meta, u32* doneList, u32* doneCount,
+                                                           u32 listBase, u32 sliceLen, unsigned long long* work2) {
+    u32 const count = zj_slice_count(countPtr, listBase, sliceLen);
+    list += listBase;
+    zj_match_run<ZLaneF<ZEEnt16> >(src, srcOff, level, list, count, workCounter, tables, tableStride, fscratch, maxSrc, meta, doneList, doneCount, work2);
 }
 
 // ---- need-gated level 3 (zj_need.h; ZJNI_NEED = 2 by default: flags for the frames zn_worth() picks) ----
@@ -722,6 +733,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void
                                                            const u32* __restrict__ list, const u32* countPtr, u32* workCounter,
                                                            u8* tables, u32 tableStride, u8* fscratch, u32 maxSrc, u32* meta, u32 listBase, u32 sliceLen, u32* doneList, u32* doneCount,
                                                            const u8* flagsBase, const u8* gate, const u32* ready) {
+    level &= ~ZE_LW_NEG;                                  // negative levels: zj_enc_match_wide_kernel_neg
     u32 const count = zj_slice_count(countPtr, listBase, sliceLen);
     list += listBase;
     // With need flags (level 3, flagsBase != nullptr): the run machine for every frame of the slice, flags of ZN_FLAG_STRIDE_WIDE bytes per entry for the frames
@@ -731,6 +743,15 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void
     // 65 536 x 128 KiB 382-441 ms with ZLaneD, 445-492 ms with ZLaneR (profiles/r04/d_, e_); tests/test_emu_encode.py keeps the machine exact at these sizes.
     if (ZE_LW_LEVEL(level) == 3) zj_match_run<ZLaneD<ZEEntTag> >(src, srcOff, level, list, count, workCounter, tables, tableStride, fscratch, maxSrc, meta, doneList, doneCount);
     else zj_match_run<ZLaneF<ZEEnt32> >(src, srcOff, level, list, count, workCounter, tables, tableStride, fscratch, maxSrc, meta, doneList, doneCount);
+}
+// negative levels, frames of list B (4-byte positions): ZLaneF with the level's step, as zj_enc_match_kernel_neg (no need flags: those are level 3's)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 2))) void zj_enc_match_wide_kernel_neg(const u8* __restrict__ src, const u64* __restrict__ srcOff, u32 level,
+                                                           const u32* __restrict__ list, const u32* countPtr, u32* workCounter,
+                                                           u8* tables, u32 tableStride, u8* fscratch, u32 maxSrc, u32* meta, u32 listBase, u32 sliceLen, u32* doneList, u32* doneCount,
+                                                           const u8* flagsBase, const u8* gate, const u32* ready) {
+    u32 const count = zj_slice_count(countPtr, listBase, sliceLen);
+    list += listBase;
+    zj_match_run<ZLaneF<ZEEnt32> >(src, srcOff, level, list, count, workCounter, tables, tableStride, fscratch, maxSrc, meta, doneList, doneCount);
 }
 // zero the first `count` slots of `stride` bytes (the table slots of a slice; nothing to do for an empty slice)
 __global__ __launch_bounds__(256) void zj_zero_slots_kernel(u8* base, u32 stride, const u32* countPtr, u32 listBase, u32 sliceLen) {
@@ -809,6 +830,7 @@ __global__ __launch_bounds__(64, ZJ_MULTI_WAVES) void zj_encode_multi_kernel(con
                                                               u64* __restrict__ result, u32 level, const u32* __restrict__ list, const u32* countPtr, u32* workCounter,
                                                               u8* scratch, u32* tables, u32 flags, u32 ldsBytes, u32 pipeMax) {
     if (zj_pipe_route(countPtr, pipeMax)) return;          // zj_encode_pipe_kernel's batch (queued ahead of this launch)
+    level &= ~ZE_LW_NEG;                                   // negative levels: zj_encode_multi_kernel_neg
     __shared__ ZEncShared sh;
 #ifdef ZX_PROFILE          /* analysis build: the entropy stage's phase marks of workgroup 0, printed when it is done (tools/ab_call*.sh) */
     __shared__ unsigned long long zxPhase[16];
@@ -844,6 +866,33 @@ __global__ __launch_bounds__(64, ZJ_MULTI_WAVES) void zj_encode_multi_kernel(con
 #endif
 }
 
+// Negative levels, list C (their multi-block frames only: single-block frames of these levels are lists A / B): the frame loop above with the
+// level's step in the one-lane parse of every block (the wave matcher ZWaveF walks step 2 only) and raw literals.  A kernel of its own so that
+// the one above keeps its registers; the pipelined kernel below does not take these levels.
+__global__ __launch_bounds__(64, ZJ_MULTI_WAVES) void zj_encode_multi_kernel_neg(const u8* __restrict__ src, const u64* __restrict__ srcOff, u8* __restrict__ dst, const u64* __restrict__ dstOff,
+                                                              u64* __restrict__ result, u32 level, const u32* __restrict__ list, const u32* countPtr, u32* workCounter,
+                                                              u8* scratch, u32* tables, u32 flags, u32 ldsBytes, u32 pipeMax) {
+    __shared__ ZEncShared sh;
+    ZjProf pf; pf.start(nullptr);
+    Grp<64> g;
+    if (threadIdx.x == 0) { sh.dictLoaded = 0; sh.ctDict[0] = 0; sh.ctDict[1] = 0; sh.ctDict[2] = 0; }
+    __syncthreads();
+    u8* const ws = scratch + (size_t)blockIdx.x * ZE_SCRATCH_BYTES;
+    u32* const tb = tables + (size_t)blockIdx.x * (ZE_MULTI_TABLE_BYTES / 4u);
+    u32 const count = ZJ_UNI(*countPtr);
+    for (;;) {
+        u32 const k = zj_next_index(workCounter);
+        if (k >= count) break;
+        u32 const i = ZJ_UNI(list[k]);
+        u64 const s0 = zj_uni64(srcOff[i]), s1 = zj_uni64(srcOff[i + 1]), d0 = zj_uni64(dstOff[i]), d1 = zj_uni64(dstOff[i + 1]);
+        u64 const cap = d1 - d0;
+        u32 const size = (u32)(s1 - s0), capU = (u32)(cap > 0xFFFFFFFFull ? 0xFFFFFFFFull : cap);
+        u64 const r = ze_compress_multi(g, sh, zj_dyn_lds, src + s0, size, dst + d0, capU, level, ws, pf, flags | ZE_FLAG_MULTI_FAST_SERIAL, tb, ldsBytes);
+        if (threadIdx.x == 0) result[i] = r;
+        __syncthreads();
+    }
+}
+
 // Multi-block frames, PIPELINED (round 6; zj_encode.h "multi-block frames, PIPELINED"): a workgroup of TWO waves per frame — wave 1 parses block b + 1 while wave 0
 // entropy-codes block b.  For batches that cannot fill the device with one-wave chains (a thousand 1 MiB frames: BASELINE config 1); with every wave slot taken the
 // one-wave kernel above does the same work in fewer wave-milliseconds, so large batches stay there (compress_batch_device_impl).  Scratch: two slots of encScratch
@@ -854,6 +903,7 @@ __global__ __launch_bounds__(128, 2) void zj_encode_pipe_kernel(const u8* __rest
                                                              u64* __restrict__ result, u32 level, const u32* __restrict__ list, const u32* countPtr, u32* workCounter,
                                                              u8* scratch, u32* tables, u32 flags, u32 ldsBytesE, u32 pipeMax) {
     if (!zj_pipe_route(countPtr, pipeMax)) return;
+    level &= ~ZE_LW_NEG;                                   // (never launched for negative levels)
     // (ONE LDS object: declared as separate variables the two waves' uniforms came out OVERLAID — group_segment_fixed_size 1 440 instead of 2 700: each is used by one
     //  role's code only, and the LDS lowering does not know that the roles run at the same time on different waves)
     struct PipeShared { ZEncShared e, p; ZEPipe pipe; u32 nextK; };
@@ -1063,6 +1113,10 @@ namespace {
 // pass-0 LDS per level: the tables of > 16 KiB inputs up to 64 KiB (u16 positions)
 #define ZJ_BIG_SLICE ((size_t)16384)    /* frames of 16-128 KiB at levels 4-8 per pass of the lane-per-frame route (655 KiB of records each) */
 #define ZJ_LEVEL_MAX 8                 /* levels 1-3 on every path; level 4 (inputs <= 128 KiB) and levels 5-8 (<= 16 KiB), no dictionary, no explicit table sizes, on the HBM-table kernel */
+#define ZJ_LEVEL_MIN (-131072)         /* ZSTD_minCLevel() = -ZSTD_TARGETLENGTH_MAX: lower levels are clamped to it, as the reference clamps them */
+// the levels the batch entries serve: 1..ZJ_LEVEL_MAX, and every negative level (zstd's --fast=N: the fast strategy with step N + 1 and raw literals,
+// on the paths of level 1 — no dictionary, no explicit table sizes, no streams).  0 means 3 and is mapped by the caller.
+static inline bool zj_level_served(int level) { return level < 0 || (level >= 1 && level <= ZJ_LEVEL_MAX); }
 size_t enc_lds_pass0(int level) {
     size_t const need = level == 1 ? (8192u * 2u) : (level == 2 ? (32768u * 2u) : (((1u << ZE_L3_HASHLOG) + (1u << ZE_L3_CHAINLOG)) * 2u));
     return need > sizeof(ZEEntropy) ? need : sizeof(ZEEntropy);
@@ -1848,6 +1902,7 @@ static size_t compress_batch_device_impl(const void* d_src, const uint64_t* d_sr
     if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
     int const level = (int)ZE_LW_LEVEL((u32)levelWord);       // kernels take the level word (level | hashLog << 8 | chainLog << 16)
     bool const tuned = ZE_LW_TUNED((u32)levelWord);
+    bool const neg = ((u32)levelWord & ZE_LW_NEG) != 0u;      // a negative level: level 1's routes, each on its *_neg kernel (zj_encode_kernel takes both)
     if (level < 1 || level > ZJ_LEVEL_MAX) return ZJNI_ERR(42);
     if (n == 0) return 0;
     if (n > 0xFFFFFFFFull) return ZJNI_ERR(72);
@@ -1900,13 +1955,14 @@ static size_t compress_batch_device_impl(const void* d_src, const uint64_t* d_sr
         // frame — 1 024 x 1 MiB: the frame's chain is the parse alone.  With the slots full the one-wave kernel does the same work in fewer wave-milliseconds.
         // ZJNI_PIPE_MAX (tuning builds): the largest batch that takes it (0: never).
         u32 pipeMax = level <= 3 ? (u32)d->pipeGrid : 0u; if (const char* ov = zj_tune("ZJNI_PIPE_MAX")) { long long const v = atoll(ov); pipeMax = v <= 0 ? 0u : ((size_t)v < (size_t)d->pipeGrid ? (u32)v : (u32)d->pipeGrid); }
+        if (neg) pipeMax = 0u;                                      // negative levels: zj_encode_multi_kernel_neg, never the pipelined kernel
         d->lastPipeMax = pipeMax;
         if (pipeMax) {
             u32 const gp = (u32)(n < (size_t)pipeMax ? n : (size_t)pipeMax);
             hipLaunchKernelGGL(zj_encode_pipe_kernel, dim3(gp), dim3(128), (u32)(((sizeof(ZEEntropy) + 15u) & ~(size_t)15) + ZJ_PIPE_LDS_P), st, (const u8*)d_src, (const u64*)d_src_off, (u8*)d_dst, (const u64*)d_dst_off,
                                (u64*)d_result, (u32)levelWord, (const u32*)listC, (const u32*)(ctr + 4), ctr + 5, d->encScratch, d->multiTables, flags | multiSerial, (u32)sizeof(ZEEntropy), pipeMax);
         }
-        hipLaunchKernelGGL(zj_encode_multi_kernel, dim3(gc), dim3(64), (u32)sizeof(ZEEntropy), st, (const u8*)d_src, (const u64*)d_src_off, (u8*)d_dst, (const u64*)d_dst_off,
+        hipLaunchKernelGGL(neg ? zj_encode_multi_kernel_neg : zj_encode_multi_kernel, dim3(gc), dim3(64), (u32)sizeof(ZEEntropy), st, (const u8*)d_src, (const u64*)d_src_off, (u8*)d_dst, (const u64*)d_dst_off,
                            (u64*)d_result, (u32)levelWord, (const u32*)listC, (const u32*)(ctr + 4), ctr + 5, d->encScratch, d->multiTables, flags | multiSerial, (u32)sizeof(ZEEntropy), pipeMax);
     }
     if (l3wave) {                                  // the whole batch was list C's
@@ -2093,7 +2149,7 @@ static size_t compress_batch_device_impl(const void* d_src, const uint64_t* d_sr
                 if (hipEventRecord(d->evJoinWave, d->waveStream) != hipSuccess) return bail(ZJNI_ERR(ZJNI_ERROR_no_device));
             }
             u32 lanePeriod = 0;                                    // rotation period of the double-fast lane machines (0 = the machine's own)
-            if (const char* ov = zj_tune("ZJNI_LANE_PERIOD")) { lanePeriod = (u32)atoi(ov) & 0xFu; if (lanePeriod && lanePeriod < 3u) lanePeriod = 3u; }     // (three non-search states take turns: a shorter rotation would never run one of them)
+            if (const char* ov = zj_tune("ZJNI_LANE_PERIOD"); ov && !neg) { lanePeriod = (u32)atoi(ov) & 0xFu; if (lanePeriod && lanePeriod < 3u) lanePeriod = 3u; }     // (three non-search states take turns: a shorter rotation would never run one of them)
             if (runMachine) {
                 void (*kern)(const u8*, const u64*, u32, const u32*, const u32*, u32*, u8*, u32, u8*, u32, u32*, u32*, u32*, u32, u32, const u8*, const u8*, const u32*) = zj_enc_match_run_kernel;
 #ifdef ZJ_TUNING_KERNELS
@@ -2111,7 +2167,7 @@ static size_t compress_batch_device_impl(const void* d_src, const uint64_t* d_sr
             }
 #endif
             else if (!waveOnly) {
-            hipLaunchKernelGGL(zj_enc_match_kernel, dim3(gridM), dim3(64), 0, st, (const u8*)d_src, (const u64*)d_src_off, (u32)levelWord | (lanePeriod << 24),
+            hipLaunchKernelGGL(neg ? zj_enc_match_kernel_neg : zj_enc_match_kernel, dim3(gridM), dim3(64), 0, st, (const u8*)d_src, (const u64*)d_src_off, (u32)levelWord | (lanePeriod << 24),
                                listM, (const u32*)ctr, mctr, tables, tableStride, fscratch, maxSrc, meta, doneList, mctr + 1, 0u, 0xFFFFFFFFu,
                                hybrid ? work2 : (unsigned long long*)nullptr);
             d->lastRoute = hybrid ? ZJ_ROUTE_HYBRID : ZJ_ROUTE_LANE;
@@ -2140,7 +2196,7 @@ static size_t compress_batch_device_impl(const void* d_src, const uint64_t* d_sr
                 hipLaunchKernelGGL(zj_enc_match_run_kernel, dim3(gridM), dim3(64), 0, st, (const u8*)d_src, (const u64*)d_src_off, (u32)levelWord,
                                    (const u32*)listA, (const u32*)ctr, mctr, tables, tableStride, fscratch, maxSrc, meta, (u32*)nullptr, (u32*)nullptr, 0u, 0xFFFFFFFFu, (const u8*)nullptr, (const u8*)nullptr, (const u32*)nullptr);
             else
-            hipLaunchKernelGGL(zj_enc_match_kernel, dim3(gridM), dim3(64), 0, st, (const u8*)d_src, (const u64*)d_src_off, (u32)levelWord,
+            hipLaunchKernelGGL(neg ? zj_enc_match_kernel_neg : zj_enc_match_kernel, dim3(gridM), dim3(64), 0, st, (const u8*)d_src, (const u64*)d_src_off, (u32)levelWord,
                                (const u32*)listA, (const u32*)ctr, mctr, tables, tableStride, fscratch, maxSrc, meta, (u32*)nullptr, (u32*)nullptr, 0u, 0xFFFFFFFFu, (unsigned long long*)nullptr);
             (void)hipEventRecord(d->tev[1], st); d->tevCompress = true;
             preclear();
@@ -2230,7 +2286,7 @@ static size_t compress_batch_device_impl(const void* d_src, const uint64_t* d_sr
                 }
             }
             (void)hipEventRecord(d->tev[8], st);
-            hipLaunchKernelGGL(zj_enc_match_wide_kernel, dim3(gridMB), dim3(64), 0, st, (const u8*)d_src, (const u64*)d_src_off, (u32)levelWord,
+            hipLaunchKernelGGL(neg ? zj_enc_match_wide_kernel_neg : zj_enc_match_wide_kernel, dim3(gridMB), dim3(64), 0, st, (const u8*)d_src, (const u64*)d_src_off, (u32)levelWord,
                                (const u32*)listB, (const u32*)(ctr + 1), wctr, tb, strideB, fs, (u32)ZE_WIDE_MAX_SRC, mt, (u32)base, (u32)sliceB, forked ? doneB : (u32*)nullptr, forked ? wctr + 2 : (u32*)nullptr,
                                (const u8*)(flagged ? flagsW : nullptr), (const u8*)(flagged ? gateW : nullptr), (const u32*)(flagged ? readyW : nullptr));
             if (flagged && hipStreamWaitEvent(st, d->evJoinWave, 0) != hipSuccess) { (void)hipStreamSynchronize(d->waveStream); (void)hipStreamSynchronize(d->sideStream); (void)hipStreamSynchronize(st); return ZJNI_ERR(ZJNI_ERROR_no_device); }
@@ -2267,6 +2323,7 @@ static int zj_level3_word(int lw) {
 }
 static size_t compress_chunked(const void* d_src, const uint64_t* d_src_off, void* d_dst, const uint64_t* d_dst_off,
                                uint64_t* d_result, size_t n, int level, u32 flags, void* stream) {
+    if (level < 0) level = (int)ZE_LW_NEGATIVE((u32)(level < ZJ_LEVEL_MIN ? -ZJ_LEVEL_MIN : -level));    // negative level -> level word (zj_encode.h: ZE_LW_NEG)
     level = zj_level3_word(level);
     BatchOrder order(cur_state(), stream);
     size_t const perFrame = ZE_LW_LEVEL((u32)level) > 3u ? (size_t)ZE_CHAIN_TABLE_BYTES + ZE_FRAME_STRIDE(ZE_CHAIN_MAX_SRC) + 21
@@ -2282,13 +2339,13 @@ static size_t compress_chunked(const void* d_src, const uint64_t* d_src_off, voi
 size_t zjni_compress_batch_device(const void* d_src, const uint64_t* d_src_off, void* d_dst, const uint64_t* d_dst_off,
                                   uint64_t* d_result, size_t n, int level, void* stream) {
     if (level == 0) level = 3;                    // ZSTD_CLEVEL_DEFAULT, as ZSTD_c_compressionLevel = 0 means
-    if (level < 1 || level > ZJ_LEVEL_MAX) return ZJNI_ERR(42);
+    if (!zj_level_served(level)) return ZJNI_ERR(42);
     return compress_chunked(d_src, d_src_off, d_dst, d_dst_off, d_result, n, level, 0u, stream);
 }
 size_t zjni_compress_batch_device2(const void* d_src, const uint64_t* d_src_off, void* d_dst, const uint64_t* d_dst_off,
                                    uint64_t* d_result, size_t n, int level, int checksum, void* stream) {
     if (level == 0) level = 3;                    // ZSTD_CLEVEL_DEFAULT, as ZSTD_c_compressionLevel = 0 means
-    if (level < 1 || level > ZJ_LEVEL_MAX) return ZJNI_ERR(42);
+    if (!zj_level_served(level)) return ZJNI_ERR(42);
     return compress_chunked(d_src, d_src_off, d_dst, d_dst_off, d_result, n, level, checksum ? ZE_FLAG_CHECKSUM : 0u, stream);
 }
 // Stream frames (include/zjni_amd.h): n streams, each buffered whole, through zj_encode_stream_kernel.
@@ -2882,7 +2939,7 @@ static size_t multi_compress_gather(const void* const* src, const size_t* srcSiz
 size_t zjni_compress_batch_multi(const void* const* src, const size_t* srcSize, void* const* dst, const size_t* dstCap, size_t* result, size_t n,
                                  int level, int checksum, const int* devices, int nDevices, int mode) {
     if (level == 0) level = 3;
-    if (level < 1 || level > ZJ_LEVEL_MAX) return ZJNI_ERR(42);
+    if (!zj_level_served(level)) return ZJNI_ERR(42);
     if (mode == 1) return multi_compress_gather(src, srcSize, dst, dstCap, result, n, level, checksum ? 1 : 0, devices, nDevices);
     return multi_run(true, src, srcSize, dst, dstCap, result, n, level, checksum ? 1 : 0, devices, nDevices);
 }
@@ -2892,13 +2949,13 @@ size_t zjni_decompress_batch_multi(const void* const* src, const size_t* srcSize
 }
 size_t zjni_compress_batch(const void* const* src, const size_t* srcSize, void* const* dst, const size_t* dstCap, size_t* result, size_t n, int level) {
     if (level == 0) level = 3;                    // ZSTD_CLEVEL_DEFAULT, as ZSTD_c_compressionLevel = 0 means
-    if (level < 1 || level > ZJ_LEVEL_MAX) return ZJNI_ERR(42);
+    if (!zj_level_served(level)) return ZJNI_ERR(42);
     return host_batch(true, src, srcSize, dst, dstCap, result, n, level);
 }
 
 size_t zjni_compress_batch2(const void* const* src, const size_t* srcSize, void* const* dst, const size_t* dstCap, size_t* result, size_t n, int level, int checksum) {
     if (level == 0) level = 3;                    // ZSTD_CLEVEL_DEFAULT, as ZSTD_c_compressionLevel = 0 means
-    if (level < 1 || level > ZJ_LEVEL_MAX) return ZJNI_ERR(42);
+    if (!zj_level_served(level)) return ZJNI_ERR(42);
     return host_batch(true, src, srcSize, dst, dstCap, result, n, level, checksum ? 1 : 0);
 }
 
@@ -2907,7 +2964,7 @@ size_t zjni_compress_batch_advanced(const void* const* src, const size_t* srcSiz
     if (level == 0) level = 3;                    // ZSTD_CLEVEL_DEFAULT, as ZSTD_c_compressionLevel = 0 means
     int lw; size_t const e = level_word(level, hashLog, chainLog, &lw);
     if (e) return e;
-    if (level < 1 || level > ZJ_LEVEL_MAX || (level > 3 && (hashLog | chainLog))) return ZJNI_ERR(42);
+    if (!zj_level_served(level) || (level > 3 && (hashLog | chainLog))) return ZJNI_ERR(42);
     return host_batch(true, src, srcSize, dst, dstCap, result, n, lw, checksum);
 }
 // ---- cross-thread aggregation of per-buffer calls (second half) ----
@@ -2985,9 +3042,11 @@ zjni_aggregator* zjni_createAggregator(int device, size_t maxBatch, unsigned max
 void zjni_freeAggregator(zjni_aggregator* a) { delete a; }        // no call may be in flight
 size_t zjni_aggregator_compress(zjni_aggregator* a, void* dst, size_t dstCap, const void* src, size_t srcSize, int level, int checksum) {
     if (level == 0) level = 3;
-    if (level < 1 || level > ZJ_LEVEL_MAX) return ZJNI_ERR(42);
+    if (!zj_level_served(level)) return ZJNI_ERR(42);
+    if (level < ZJ_LEVEL_MIN) level = ZJ_LEVEL_MIN;
     ZjAggReq rq = { src, srcSize, dst, dstCap, 0 };
-    return agg_submit(a, level * 2 + (checksum ? 1 : 0), rq, level, checksum ? 1 : 0);
+    int const kind = (level > 0 ? level * 2 : 32 - level * 2) + (checksum ? 1 : 0);      // compress kinds: 2..17 for levels 1-8, from 34 on for negative levels; decompress is -1
+    return agg_submit(a, kind, rq, level, checksum ? 1 : 0);
 }
 size_t zjni_aggregator_decompress(zjni_aggregator* a, void* dst, size_t dstCap, const void* src, size_t srcSize) {
     ZjAggReq rq = { src, srcSize, dst, dstCap, 0 };

@@ -348,7 +348,7 @@ struct ZLaneF {
     const u8* src; u32 n, ilimit; Ent* T; ZLHash hT;
     ZEOut o;
     u32 st, cont, lastLL;
-    u32 ip0, ip1, ip2, ip3, anchor, rep1, rep2, step, nextStep, cur0, period;
+    u32 ip0, ip1, ip2, ip3, anchor, rep1, rep2, step, nextStep, cur0, period, stepSize;
     u64 w0, w1, w2, w3, wIns; u32 eX, eY;                 // eX / eY: table entries of ip0 / ip1 as the reference reads them
     u32 ca, cb, acc, mpos, mLength, offcode, bk;
     bool more, needBack, chk, haveIns;               // wIns/haveIns: the word at cur0 + 2 (first post-insert) when the search round already holds it
@@ -357,12 +357,13 @@ struct ZLaneF {
         src = s; n = size; ilimit = size - 8u; hT = zl_hash_of(p.minMatch, p.hashLog); T = (Ent*)table;
         o.seqs = (ZESeq*)fscratch; o.litOff = (u32*)(fscratch + (size_t)ZE_FRAME_MAXSEQ(maxSrc) * 16u); o.n = 0; o.lit = 0;
         ip0 = 1; anchor = 0; rep1 = 1; rep2 = 0; chk = false; lastLL = size; needBack = more = haveIns = false; bk = 0;
+        stepSize = p.targetLength + (p.targetLength == 0u ? 1u : 0u) + 1u;      // zstd_fast.c:200: 2 at levels 1-2, the acceleration + 1 at negative levels
         period = p.hashLog >= 15u ? 4u : 5u;          // measured: level 1 (hashLog 13) 84.0 ms at 5 / 85.3 at 4 / 99.0 at 3; level 2 (hashLog 15) 137.3 / 132.1 / 139.2
         st = ZL_LOADW;
     }
     ZJ_DEV_MEMBER void finish() { lastLL = n - anchor; st = ZL_DONE; }
     ZJ_DEV_MEMBER void outer() {
-        step = 2; nextStep = ip0 + 128u; ip1 = ip0 + 1u; ip2 = ip0 + 2u; ip3 = ip0 + 3u;
+        step = stepSize; nextStep = ip0 + 128u; ip1 = ip0 + 1u; ip2 = ip0 + step; ip3 = ip2 + 1u;
         if (ip3 >= ilimit) finish(); else st = ZL_START;
     }
     ZJ_DEV_MEMBER void begin_count(u32 a, u32 b, u32 c) { ca = a; cb = b; acc = 0; cont = c; st = ZL_COUNT; }

@@ -443,7 +443,7 @@ static int gpu_takes_when(const CtxState* s, jint srcSize, int on) {
     }
     if (s->cdict || s->localCdict) return s->contentSize;              /* sizes the library does not take come back as 40 / 201 and are forwarded */
     if (s->level >= 4 && s->level <= 8) return (size_t)srcSize <= (s->level == 4 ? ZJNI_LEVEL4_MAX : ZJNI_LAZY_MAX) && !(s->hashLog | s->chainLog);   /* one block, no explicit table sizes */
-    return s->level >= 0 && s->level <= 3 && (size_t)srcSize <= ZJNI_FRAME_MAX;       /* beyond the level's window the library answers 201 and the call is forwarded */
+    return s->level <= 3 && (size_t)srcSize <= ZJNI_FRAME_MAX;       /* levels 0-3 and every negative level; beyond the level's window the library answers 201 and the call is forwarded */
 }
 static int gpu_takes(const CtxState* s, jint srcSize) {           /* the one-shot natives: ZSTD_CCtx_reset(session_only) comes first, and forgets a pledged size */
     if (s) ((CtxState*)s)->hasPledged = 0;
@@ -628,7 +628,7 @@ JNIEXPORT jlong JNICALL P(Zstd_getFrameContentSize0)(JNIEnv* env, jclass cls, jb
 }
 JNIEXPORT jlong JNICALL P(Zstd_compressUnsafe)
   (JNIEnv* env, jclass cls, jlong dst, jlong dst_size, jlong src, jlong src_size, jint level, jboolean checksumFlag) {
-    if (per_buffer_on_gpu() && level >= 0 && (level <= 3 ? (size_t)src_size <= ZJNI_FRAME_MAX : (level <= 8 && (size_t)src_size <= (level == 4 ? ZJNI_LEVEL4_MAX : ZJNI_LAZY_MAX)))) {
+    if (per_buffer_on_gpu() && (level <= 3 ? (size_t)src_size <= ZJNI_FRAME_MAX : (level <= 8 && (size_t)src_size <= (level == 4 ? ZJNI_LEVEL4_MAX : ZJNI_LAZY_MAX)))) {
         size_t const r = zjni_compress2((void*)(intptr_t)dst, (size_t)dst_size, (const void*)(intptr_t)src, (size_t)src_size, level, checksumFlag == JNI_TRUE);
         if (gpu_result_final(r)) return (jlong)r;
     }
