@@ -79,7 +79,7 @@ size_t zjni_decompress_batch_device(const void* d_src, const uint64_t* d_src_off
  * entries only: no dictionary, no explicit table sizes; a wave-per-frame kernel with one lane parsing — exact, not fast).  Negative levels (zstd's
  * --fast=N, down to ZSTD_minCLevel() = -131072; lower ones are clamped to it, as the reference clamps them): the fast strategy with the parameters of
  * row 0 of the size's table, the match loop stepping N + 1 and raw literals, on level 1's routes (every entry that takes a level, the blocking
- * ones, the aggregator, begin/finish and the multi-device entry included; no dictionary, no explicit table sizes, no streams).  Buffers larger than
+ * ones, the aggregator, begin/finish and the multi-device entry included; no explicit table sizes; dictionaries and streams at these levels: below).  Buffers larger than
  * ZJNI_BLOCKSIZE_MAX become multi-block frames (one wavefront per frame, block after block; see ZJNI_FRAME_MAX for the
  * range); beyond it d_result[i] reports ZJNI_ERROR_unsupported and the buffer stays on the CPU path.
  * Destination capacity (d_dst_off[i+1] - d_dst_off[i]): with zjni_compressBound(srcSize) a frame always fits.  With less, the answer is
@@ -143,7 +143,8 @@ size_t zjni_compress_batch_advanced(const void* const* src, const size_t* srcSiz
  * BUFFERED UNTIL IT IS CLOSED, at most the level's unknown-size window (levels 1 / 2 / 3: 512 KiB / 1 MiB / 2 MiB): the frame ZSTD_compressStream2
  * produces without a pledged size, byte for byte (N/compress/zstd_compress.c:6103-6300, :4591-4692) — the level's default parameter row whatever
  * the total, no content size in the header, the input cut into the stream's 128 KiB pieces, blocks ended where the caller flushed, the empty raw
- * last block, the checksum.  flushAt[0 .. nFlush): ascending byte counts after which the caller flushed.  final_ = 0: flushed, not closed — returns the
+ * last block, the checksum.  Negative levels (zstd's --fast=N, clamped at -131072): row 0 of that table (window 19, chain 12, hash 13, minMatch 6),
+ * the match loop stepping N + 1, raw literals, level 1's 512 KiB window.  flushAt[0 .. nFlush): ascending byte counts after which the caller flushed.  final_ = 0: flushed, not closed — returns the
  * frame's beginning up to the last flush (the bytes a later call with more input reproduces and continues).  knownEmpty: the stream was closed before
  * any other call (its size, 0, is then known: single-segment header).  201 above the window, 42 above level 3: the bundled library's stream.
  * The device form takes n streams: stream i = blob[off[i], off[i + 1]), its flush positions d_flush_at[d_flush_off[i] .. d_flush_off[i + 1]) (d_flush_off may be
@@ -163,8 +164,10 @@ size_t zjni_compress_stream_batch_device(const void* d_src, const uint64_t* d_sr
  * zjni_cdict == ZSTD_CDict as zstd-jni holds it in ZstdDictCompress.nativePtr (J/ZstdDictCompress.java;
  * N/jni_fast_zstd.c:18-66: init = ZSTD_createCDict(dict, size, level), free = ZSTD_freeCDict).  The dictionary is
  * digested once on the device: parameters of (level, dictSize), tagged hash tables over the content, the entropy
- * tables and repcodes of its header.  Levels 1..3.  NULL for a corrupted dictionary, a bad level, fewer than
- * 8 bytes, or without a device. */
+ * tables and repcodes of its header.  Levels 1..3, and every negative level (zstd's --fast=N; below ZSTD_minCLevel() = -131072
+ * clamped to it): row 0 of the table the dictionary's size picks (N/compress/clevels.h), targetLength = N, the fast strategy's digest; its
+ * frames step N in the attach-mode search and N + 1 in copy mode, with raw literals (N/compress/zstd_fast.c:491, :717;
+ * zstd_compress_internal.h:685).  NULL for a corrupted dictionary, a level above 3, fewer than 8 bytes, or without a device. */
 typedef struct zjni_cdict zjni_cdict;
 zjni_cdict* zjni_createCDict(const void* dict, size_t dictSize, int level);
 size_t zjni_freeCDict(zjni_cdict* cdict);
@@ -176,7 +179,8 @@ unsigned zjni_getDictID_fromCDict(const zjni_cdict* cdict);
  * it is double-fast) and, beyond them up to one block (128 KiB), its copy mode (ZSTD_resetCCtx_byCopyingCDict,
  * N/compress/zstd_compress.c:2402-2468: the dictionary as an external segment) as long as the reference compresses with
  * the dictionary's own parameters (srcSize < 128 KiB or < 6 x the dictionary's content, :5256-5257); otherwise the
- * result slot reports ZSTD_error_parameter_unsupported (more than one block: ZJNI_ERROR_unsupported). */
+ * result slot reports ZSTD_error_parameter_unsupported (more than one block: ZJNI_ERROR_unsupported).  The same at every level
+ * the CDict was made for, negative levels included. */
 size_t zjni_compress_batch_device_usingCDict(const void* d_src, const uint64_t* d_src_off,
                                              void* d_dst, const uint64_t* d_dst_off,
                                              uint64_t* d_result, size_t n, const zjni_cdict* cdict, int checksum, void* stream);

@@ -9,6 +9,7 @@
 // zstd_compress.c:2309-2385 (attach decision and working parameters), zstd_fast.c:483-679 and
 // zstd_double_fast.c:328-547 (the dictMatchState searches).  N/ = src/main/native/.
 //
+// Levels: 1..3 and every negative level (zstd's --fast=N: row 0 of the table, targetLength = N, raw literals; the CDict's level word carries N).
 // Scope: the attach range — sources up to 8 KiB (fast) / 16 KiB (double-fast), where the reference searches the
 // dictionary's own tables in place (ZSTD_shouldAttachDict).  Larger sources with a dictionary make the reference copy
 // or reload the dictionary into the working tables (extDict search); those get ZJ_E_PARAM_UNSUPPORTED here.
@@ -41,6 +42,34 @@ ZJ_HD ZEParams ze_cdict_params(u32 level, u32 dictSize) {
     ZEParams p; p.windowLog = w; p.chainLog = c; p.hashLog = h; p.minMatch = mm; p.strategy = st;
     return p;
 }
+// The same for a negative level (zstd's --fast=N; `lw` its level word, zj_encode.h ZE_LW_NEG): row 0 of the table rSize picks ("base for negative
+// levels", clevels.h:28,54,80,106), targetLength = the acceleration (zstd_compress.c:7768-7777), then the same unknown-size adjustment.  The fast
+// strategy with a hash log never above level 1's for the same dictionary (13 / 12 / 13 / 13 against 15 / 13 / 14 / 14): the table strides and LDS
+// slots sized for level 1 hold these tables too.
+ZJ_HD ZEParams ze_cdict_params_neg(u32 lw, u32 dictSize) {
+    u64 const rSize = (u64)dictSize + 499u;
+    u32 w, c, h, mm;
+    if (rSize <= (16u << 10)) { w = 14; c = 12; h = 13; mm = 5; }
+    else if (rSize <= (128u << 10)) { w = 17; c = 12; h = 12; mm = 5; }
+    else if (rSize <= (256u << 10)) { w = 18; c = 12; h = 13; mm = 5; }
+    else { w = 19; c = 12; h = 13; mm = 6; }
+    {   u32 const tSize = 513u + dictSize;
+        u32 const srcLog = zj_hibit(tSize - 1) + 1;
+        if (w > srcLog) w = srcLog;
+        u32 dawl = w;
+        if (((u64)1 << w) < (u64)dictSize + 513u) dawl = zj_hibit((u32)(dictSize + (1u << w)) - 1) + 1;
+        if (h > dawl + 1) h = dawl + 1;
+        if (c > dawl) c = dawl;
+        if (w < 10) w = 10;
+    }
+    ZEParams p; p.windowLog = w; p.chainLog = c; p.hashLog = h; p.minMatch = mm; p.strategy = 1; p.searchLog = 1; p.targetLength = ZE_LW_ACCEL(lw);
+    return p;
+}
+// either kind of level: 1..3, or a negative level's word
+ZJ_HD ZEParams ze_cdict_params_of(u32 lw, u32 dictSize) { return (lw & ZE_LW_NEG) ? ze_cdict_params_neg(lw, dictSize) : ze_cdict_params(lw, dictSize); }
+// the fast loops' steps at a dictionary's level (targetLength = the acceleration, 0 at levels 1-2): the dictMatchState loop steps targetLength + !targetLength
+// (zstd_fast.c:491, no + 1), the extDict loop of copy mode one more (:717, as ze_fast_step)
+ZJ_HD u32 ze_dms_step(u32 lw) { u32 const a = ZE_LW_ACCEL(lw); return a + (a == 0u ? 1u : 0u); }
 ZJ_HD u32 ze_cdict_table_entries(const ZEParams& p) { return (1u << p.hashLog) + (p.strategy == 2 ? (1u << p.chainLog) : 0u); }
 // largest source the reference compresses against the dictionary's tables in place (attachDictSizeCutoffs, zstd_compress.c:2296-2307)
 ZJ_HD u32 ze_attach_cutoff(u32 strategy) { return strategy == 2 ? (16u << 10) : (8u << 10); }
@@ -67,10 +96,10 @@ ZJ_DEV u32 ze_ncount_repeat(const short* norm, u32 dictMaxSV, u32 maxSV) {
 
 // One workgroup digests the dictionary: ZSTD_initCDict_internal -> ZSTD_compress_insertDictionary (zstd_compress.c:5551-5603,
 // :5194-5228).  `out` (header + zeroed tables + raw bytes) is in HBM; `sh`/`e` are LDS scratch.
+// `cp`: the dictionary's parameters (ze_cdict_params / ze_cdict_params_neg of `level`, which is stored as the CDict's level word).
 template <class G>
-ZJ_DEV void ze_cdict_digest(const G& g, ZDecShared& sh, ZEEntropy& e, u32 dictSize, u32 level, ZECDictDev* out) {
+ZJ_DEV void ze_cdict_digest(const G& g, ZDecShared& sh, ZEEntropy& e, u32 dictSize, u32 level, ZECDictDev* out, const ZEParams& cp) {
     const u8* const dict = (const u8*)out + out->rawOff;
-    ZEParams const cp = ze_cdict_params(level, dictSize);
     GRP_SERIAL(g) {
         u32 err = 0, contentOff = 0, hasEntropy = 0, dictID = 0;
         out->level = level; out->windowLog = cp.windowLog; out->chainLog = cp.chainLog; out->hashLog = cp.hashLog; out->minMatch = cp.minMatch; out->strategy = cp.strategy;
@@ -180,6 +209,10 @@ ZJ_DEV void ze_cdict_digest(const G& g, ZDecShared& sh, ZEEntropy& e, u32 dictSi
     }
     zj_mem_order();
     g.sync();
+}
+template <class G>
+ZJ_DEV void ze_cdict_digest(const G& g, ZDecShared& sh, ZEEntropy& e, u32 dictSize, u32 level, ZECDictDev* out) {
+    ze_cdict_digest(g, sh, e, dictSize, level, out, ze_cdict_params(level, dictSize));
 }
 
 // ------------------------------------------------------------------ attach-mode searches ----------
@@ -331,11 +364,12 @@ stored:
     return (u32)(iend - anchor);
 }
 
-// ZSTD_compressBlock_fast_dictMatchState_generic (zstd_fast.c:483-679), stepSize 1 (targetLength 0 at levels 1-2)
+// ZSTD_compressBlock_fast_dictMatchState_generic (zstd_fast.c:483-679); stepSize = targetLength + !targetLength (ze_dms_step): 1 at levels 1-2,
+// the acceleration N at negative levels (kStepIncr stays 1 << kSearchStrength)
 template <class E>
-ZJ_DEV u32 ze_block_fast_dms(ZEOut& o, const u8* src, u32 srcSize, u32 hlog, u32 mls, typename E::T* table, const ZEDms& d, u32 rep0, u32 rep1) {
+ZJ_DEV u32 ze_block_fast_dms(ZEOut& o, const u8* src, u32 srcSize, u32 hlog, u32 mls, typename E::T* table, const ZEDms& d, u32 rep0, u32 rep1, u32 stepSize = 1u) {
     const u8* const istart = src; const u8* const iend = src + srcSize; const u8* const ilimit = iend - 8;
-    const u8* ip0 = istart; const u8* ip1 = ip0 + 1; const u8* anchor = istart;
+    const u8* ip0 = istart; const u8* ip1 = ip0 + stepSize; const u8* anchor = istart;
     const u8* const dictStart = d.content; const u8* const dictEnd = d.content + d.size;
     u32 const dsz = d.size;
     u32 off1 = rep0, off2 = rep1;
@@ -347,7 +381,7 @@ ZJ_DEV u32 ze_block_fast_dms(ZEOut& o, const u8* src, u32 srcSize, u32 hlog, u32
         bool dTag = (dE & 0xFFu) == (dht0 & 0xFFu);
         u32 mE = table[hash0];
         u32 curr = (u32)(ip0 - istart);
-        u32 step = 1;
+        u32 step = stepSize;
         const u8* nextStep = ip0 + 256;
         bool got = false;
         for (;;) {
@@ -417,7 +451,7 @@ ZJ_DEV u32 ze_block_fast_dms(ZEOut& o, const u8* src, u32 srcSize, u32 hlog, u32
                 break;
             }
         }
-        ip1 = ip0 + 1;
+        ip1 = ip0 + stepSize;
     }
     return (u32)(iend - anchor);
 }
@@ -433,7 +467,8 @@ struct ZEExt { const u8* src; const u8* dict; u32 dictSize, prefixStartIndex; };
 ZJ_DEV const u8* ze_ext_ptr(const ZEExt& x, u32 idx) { return idx < x.prefixStartIndex ? x.dict + (idx - 2u) : x.src + (idx - x.prefixStartIndex); }
 ZJ_DEV bool ze_ext_overlap_ok(u32 prefixStartIndex, u32 repIndex) { return (u32)((prefixStartIndex - 1u) - repIndex) >= 3u; }   // ZSTD_index_overlap_check
 
-ZJ_DEV u32 ze_block_fast_ext(ZEOut& o, const u8* src, u32 srcSize, const u8* dict, u32 dictSize, u32 hlog, u32 mls, u32* hashTable, u32 rep0, u32 rep1) {
+// stepSize = targetLength + !targetLength + 1 (ze_fast_step): 2 at levels 1-2, N + 1 at negative levels (kStepIncr stays 1 << (kSearchStrength - 1))
+ZJ_DEV u32 ze_block_fast_ext(ZEOut& o, const u8* src, u32 srcSize, const u8* dict, u32 dictSize, u32 hlog, u32 mls, u32* hashTable, u32 rep0, u32 rep1, u32 stepSize = 2u) {
     ZEExt x; x.src = src; x.dict = dict; x.dictSize = dictSize; x.prefixStartIndex = 2u + dictSize;
     u32 const dictStartIndex = 2u, prefixStartIndex = x.prefixStartIndex;
     const u8* const istart = src; const u8* const iend = src + srcSize; const u8* const ilimit = iend - 8;
@@ -446,7 +481,7 @@ ZJ_DEV u32 ze_block_fast_ext(ZEOut& o, const u8* src, u32 srcSize, const u8* dic
         if (off2 >= maxRep) off2 = 0;
         if (off1 >= maxRep) off1 = 0; }
     for (;;) {                                                 // _start
-        u32 step = 2; const u8* nextStep = ip0 + 128;          // stepSize = targetLength + !targetLength + 1 with targetLength 0; kStepIncr
+        u32 step = stepSize; const u8* nextStep = ip0 + 128;   // stepSize; kStepIncr
         ip1 = ip0 + 1; ip2 = ip0 + step; ip3 = ip2 + 1;
         if (ip3 >= ilimit) break;
         u32 hash0 = ze_hash(ip0, hlog, mls), hash1 = ze_hash(ip1, hlog, mls);
@@ -612,16 +647,17 @@ ZJ_DEV void ze_cdict_copy_tables(const G& g, const ZECDictDev* cd, u32* slot) {
     u32 const entries = (1u << cd->hashLog) + (cd->strategy == 2 ? (1u << cd->chainLog) : 0u);
     GRP_FOR(g, i, entries) slot[i] = t[i] >> ZC_TAG_BITS;
 }
-ZJ_DEV void ze_cdict_copy_parse(const ZECDictDev* cd, const u8* src, u32 srcSize, u32* slot, u8* ws, u32* meta) {
+// step: the fast extDict loop's (ze_fast_step of the CDict's level word; 2 at levels 1-2)
+ZJ_DEV void ze_cdict_copy_parse(const ZECDictDev* cd, const u8* src, u32 srcSize, u32* slot, u8* ws, u32* meta, u32 step = 2u) {
     ZEOut o; o.seqs = (ZESeq*)(ws + ZE_WS_SEQ); o.litOff = (u32*)(ws + ZE_WS_BODY); o.n = 0; o.lit = 0;
     const u8* const dict = ze_cdict_content(cd);
-    u32 const lastLL = cd->strategy == 1 ? ze_block_fast_ext(o, src, srcSize, dict, cd->contentSize, cd->hashLog, cd->minMatch, slot, cd->rep[0], cd->rep[1])
+    u32 const lastLL = cd->strategy == 1 ? ze_block_fast_ext(o, src, srcSize, dict, cd->contentSize, cd->hashLog, cd->minMatch, slot, cd->rep[0], cd->rep[1], step)
                                          : ze_block_dfast_ext(o, src, srcSize, dict, cd->contentSize, cd->hashLog, cd->chainLog, cd->minMatch, slot, slot + (1u << cd->hashLog), cd->rep[0], cd->rep[1]);
     meta[0] = o.n; meta[1] = o.lit + lastLL; meta[2] = lastLL;
 }
 
-// The caller has zeroed `table` (ZC_TABLE_STRIDE bytes) and checked srcSize <= ze_attach_cutoff().
-ZJ_DEV void ze_match_lane_dict(const u8* src, u32 srcSize, const ZECDictDev* cd, u8* table, u8* fscratch, u32 maxSrc, u32* meta) {
+// The caller has zeroed `table` (ZC_TABLE_STRIDE bytes) and checked srcSize <= ze_attach_cutoff().  dmsStep: ze_dms_step of the CDict's level word.
+ZJ_DEV void ze_match_lane_dict(const u8* src, u32 srcSize, const ZECDictDev* cd, u8* table, u8* fscratch, u32 maxSrc, u32* meta, u32 dmsStep = 1u) {
     ZEOut o; o.seqs = (ZESeq*)fscratch; o.litOff = (u32*)(fscratch + (size_t)ZE_FRAME_MAXSEQ(maxSrc) * 16u); o.n = 0; o.lit = 0;
     u32 lastLL = srcSize;
     if (srcSize >= 7) {                                                           // ZSTD_buildSeqStore: MIN_CBLOCK_SIZE + 3 + 1 + 1
@@ -629,7 +665,7 @@ ZJ_DEV void ze_match_lane_dict(const u8* src, u32 srcSize, const ZECDictDev* cd,
         ZEParams const p = ze_attach_params(cdp, srcSize);
         ZEDms const d = ze_dms_of(cd);
         u16* const t = (u16*)table;
-        if (p.strategy == 1) lastLL = ze_block_fast_dms<ZEEnt16>(o, src, srcSize, p.hashLog, p.minMatch, t, d, cd->rep[0], cd->rep[1]);
+        if (p.strategy == 1) lastLL = ze_block_fast_dms<ZEEnt16>(o, src, srcSize, p.hashLog, p.minMatch, t, d, cd->rep[0], cd->rep[1], dmsStep);
         else lastLL = ze_block_dfast_dms<ZEEnt16>(o, src, srcSize, p.hashLog, p.chainLog, p.minMatch, t, t + (1u << p.hashLog), d, cd->rep[0], cd->rep[1]);
     }
     meta[0] = o.n; meta[1] = o.lit + lastLL; meta[2] = lastLL;

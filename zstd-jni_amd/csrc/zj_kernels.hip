@@ -1009,6 +1009,14 @@ __global__ __launch_bounds__(64) void zj_cdict_digest_kernel(u32 dictSize, u32 l
     Grp<64> g;
     ze_cdict_digest(g, sh, e, dictSize, level, out);
 }
+// the same at a negative level (`level`: its word, zj_encode.h ZE_LW_NEG): row 0's parameters (zj_cdict.h ze_cdict_params_neg).  A kernel of its own so that
+// the one above keeps its registers.
+__global__ __launch_bounds__(64) void zj_cdict_digest_kernel_neg(u32 dictSize, u32 level, ZECDictDev* out) {
+    __shared__ ZDecShared sh;
+    __shared__ ZEEntropy e;
+    Grp<64> g;
+    ze_cdict_digest(g, sh, e, dictSize, level, out, ze_cdict_params_neg(level, dictSize));
+}
 
 // Attach-mode match finding against a dictionary, lane per frame (zj_cdict.h): the dictionary's tables and content
 // are shared by every lane (L2-resident), each frame's own tables sit in its HBM slot.  Frames outside the attach
@@ -1025,6 +1033,22 @@ __global__ __launch_bounds__(64) void zj_enc_match_dict_kernel(const u8* __restr
         u64 const s0 = srcOff[i]; u64 const size = srcOff[i + 1] - s0;
         if (size > cutoff) continue;
         ze_match_lane_dict(src + s0, (u32)size, cd, tables + (size_t)k * ZC_TABLE_STRIDE, fscratch + (size_t)k * ZE_FRAME_STRIDE(ZC_MAX_SRC), ZC_MAX_SRC, meta + 3 * (size_t)k);
+    }
+}
+// a CDict of a negative level: the same search stepping the acceleration N (ze_dms_step; step 1 at compile time above, whose registers stay as they were)
+__global__ __launch_bounds__(64) void zj_enc_match_dict_kernel_neg(const u8* __restrict__ src, const u64* __restrict__ srcOff, const ZECDictDev* __restrict__ cd,
+                                                                    const u32* __restrict__ list, const u32* countPtr, u32* workCounter,
+                                                                    u8* tables, u8* fscratch, u32* meta) {
+    u32 const count = *countPtr;
+    u32 const cutoff = ze_attach_cutoff(cd->strategy);
+    u32 const step = ze_dms_step(cd->level);
+    for (;;) {
+        u32 const k = atomicAdd(workCounter, 1u);
+        if (k >= count) break;
+        u32 const i = list[k];
+        u64 const s0 = srcOff[i]; u64 const size = srcOff[i + 1] - s0;
+        if (size > cutoff) continue;
+        ze_match_lane_dict(src + s0, (u32)size, cd, tables + (size_t)k * ZC_TABLE_STRIDE, fscratch + (size_t)k * ZE_FRAME_STRIDE(ZC_MAX_SRC), ZC_MAX_SRC, meta + 3 * (size_t)k, step);
     }
 }
 
@@ -1065,6 +1089,39 @@ __global__ __launch_bounds__(64) void zj_encode_cdict_copy_kernel(const u8* __re
         __syncthreads();
         ZEPre pre; pre.seqs = (ZESeq*)(ws + ZE_WS_SEQ); pre.litOff = (const u32*)(ws + ZE_WS_BODY); pre.meta = metaL; pre.copyMode = 1u;
         u64 const r = ze_compress(g, sh, zj_dyn_lds, src + s0, size, dst + d0, (u32)(cap > 0xFFFFFFFFull ? 0xFFFFFFFFull : cap), ZJ_UNI(cd->level), ws, pf, &pre, flags, cd, ldsBytes);
+        if (threadIdx.x == 0) result[i] = r;
+        __syncthreads();
+    }
+}
+// a CDict of a negative level: the extDict parse steps N + 1 (ze_fast_step of the CDict's word); the entropy stage takes the word too (raw literals).
+// A kernel of its own so that the one above keeps its constant step and its registers.
+__global__ __launch_bounds__(64) void zj_encode_cdict_copy_kernel_neg(const u8* __restrict__ src, const u64* __restrict__ srcOff, u8* __restrict__ dst, const u64* __restrict__ dstOff,
+                                                                       u64* __restrict__ result, u32 n, const ZECDictDev* __restrict__ cd, const u32* copyCount, u32* workCounter,
+                                                                       u8* scratch, u32* tables, u32 flags, u32 ldsBytes) {
+    if (*copyCount == 0) return;
+    __shared__ ZEncShared sh;
+    __shared__ u32 metaL[4];
+    ZjProf pf; pf.start(nullptr);
+    Grp<64> g;
+    if (threadIdx.x == 0) { sh.dictLoaded = 0; sh.ctDict[0] = 0; sh.ctDict[1] = 0; sh.ctDict[2] = 0; }
+    __syncthreads();
+    u8* const ws = scratch + (size_t)blockIdx.x * ZE_SCRATCH_BYTES;
+    u32* const tb = tables + (size_t)blockIdx.x * (ZE_MULTI_TABLE_BYTES / 4u);
+    u32 const strategy = ZJ_UNI(cd->strategy), content = ZJ_UNI(cd->contentSize), lw = ZJ_UNI(cd->level);
+    for (;;) {
+        u32 const i = zj_next_index(workCounter);
+        if (i >= n) break;
+        u64 const s0 = zj_uni64(srcOff[i]), s1 = zj_uni64(srcOff[i + 1]), d0 = zj_uni64(dstOff[i]), d1 = zj_uni64(dstOff[i + 1]);
+        if (s1 - s0 > ZE_BLOCK_MAX || !ze_cdict_copy_mode(strategy, (u32)(s1 - s0), content)) continue;
+        u32 const size = (u32)(s1 - s0); u64 const cap = d1 - d0;
+        ze_cdict_copy_tables(g, cd, tb);
+        zj_mem_order();
+        __syncthreads();
+        if (threadIdx.x == 0) ze_cdict_copy_parse(cd, src + s0, size, tb, ws, metaL, ze_fast_step(lw));
+        zj_mem_order();
+        __syncthreads();
+        ZEPre pre; pre.seqs = (ZESeq*)(ws + ZE_WS_SEQ); pre.litOff = (const u32*)(ws + ZE_WS_BODY); pre.meta = metaL; pre.copyMode = 1u;
+        u64 const r = ze_compress(g, sh, zj_dyn_lds, src + s0, size, dst + d0, (u32)(cap > 0xFFFFFFFFull ? 0xFFFFFFFFull : cap), lw, ws, pf, &pre, flags, cd, ldsBytes);
         if (threadIdx.x == 0) result[i] = r;
         __syncthreads();
     }
@@ -1115,8 +1172,10 @@ namespace {
 #define ZJ_LEVEL_MAX 8                 /* levels 1-3 on every path; level 4 (inputs <= 128 KiB) and levels 5-8 (<= 16 KiB), no dictionary, no explicit table sizes, on the HBM-table kernel */
 #define ZJ_LEVEL_MIN (-131072)         /* ZSTD_minCLevel() = -ZSTD_TARGETLENGTH_MAX: lower levels are clamped to it, as the reference clamps them */
 // the levels the batch entries serve: 1..ZJ_LEVEL_MAX, and every negative level (zstd's --fast=N: the fast strategy with step N + 1 and raw literals,
-// on the paths of level 1 — no dictionary, no explicit table sizes, no streams).  0 means 3 and is mapped by the caller.
+// on the paths of level 1 — no explicit table sizes; CDicts and streams at these levels: zjni_createCDict, zjni_compress_stream*).  0 means 3 and is mapped by the caller.
 static inline bool zj_level_served(int level) { return level < 0 || (level >= 1 && level <= ZJ_LEVEL_MAX); }
+// a negative level's word (zj_encode.h: ZE_LW_NEG, the acceleration clamped as ZSTD_minCLevel() clamps it); other levels stay as they are
+static inline int zj_negative_word(int level) { return level < 0 ? (int)ZE_LW_NEGATIVE((u32)(level < ZJ_LEVEL_MIN ? -ZJ_LEVEL_MIN : -level)) : level; }
 size_t enc_lds_pass0(int level) {
     size_t const need = level == 1 ? (8192u * 2u) : (level == 2 ? (32768u * 2u) : (((1u << ZE_L3_HASHLOG) + (1u << ZE_L3_CHAINLOG)) * 2u));
     return need > sizeof(ZEEntropy) ? need : sizeof(ZEEntropy);
@@ -1589,7 +1648,7 @@ int zjni_kernel_info(int* decodeGrid, int* decodeLds, int* encodeGrid, int* enco
     return 0;
 }
 
-struct zjni_cdict { int ordinal; u8* buf; unsigned dictID; int level; u32 strategy; };   // buf = [ZECDictDev][tagged tables][raw dictionary bytes]
+struct zjni_cdict { int ordinal; u8* buf; unsigned dictID; int level; u32 strategy; };   // buf = [ZECDictDev][tagged tables][raw dictionary bytes]; level: the level word (1..3, or ZE_LW_NEG | N)
 struct zjni_ddict { int ordinal; u8* buf; size_t rawSize; unsigned dictID; };   // buf = [ZDDictDev][raw dictionary bytes]
 
 // Scratch of the multi-block stages (zj_decode_split.h): tables and records per BLOCK, claimed on the device — ZD_MB_BLOCKS blocks (4 GiB of input at 128 KiB a block)
@@ -2323,7 +2382,7 @@ static int zj_level3_word(int lw) {
 }
 static size_t compress_chunked(const void* d_src, const uint64_t* d_src_off, void* d_dst, const uint64_t* d_dst_off,
                                uint64_t* d_result, size_t n, int level, u32 flags, void* stream) {
-    if (level < 0) level = (int)ZE_LW_NEGATIVE((u32)(level < ZJ_LEVEL_MIN ? -ZJ_LEVEL_MIN : -level));    // negative level -> level word (zj_encode.h: ZE_LW_NEG)
+    level = zj_negative_word(level);              // negative level -> level word (zj_encode.h: ZE_LW_NEG)
     level = zj_level3_word(level);
     BatchOrder order(cur_state(), stream);
     size_t const perFrame = ZE_LW_LEVEL((u32)level) > 3u ? (size_t)ZE_CHAIN_TABLE_BYTES + ZE_FRAME_STRIDE(ZE_CHAIN_MAX_SRC) + 21
@@ -2352,7 +2411,8 @@ size_t zjni_compress_batch_device2(const void* d_src, const uint64_t* d_src_off,
 size_t zjni_compress_stream_batch_device(const void* d_src, const uint64_t* d_src_off, void* d_dst, const uint64_t* d_dst_off, uint64_t* d_result, size_t n, int level, int checksum,
                                          const uint32_t* d_flush_at, const uint64_t* d_flush_off, const uint32_t* d_mode, void* stream) {
     if (level == 0) level = 3;
-    if (level < 1 || level > 3) return ZJNI_ERR(42);                 // the levels whose multi-block frames the kernels make (above: the bundled library's)
+    if (level > 3) return ZJNI_ERR(42);                              // the levels whose multi-block frames the kernels make (above: the bundled library's)
+    level = zj_negative_word(level);                                 // negative levels: row 0 of the unknown-size table, step N + 1, raw literals (ze_compress_stream)
     DevState* d = cur_state();
     if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
     if (n == 0) return 0;
@@ -2374,8 +2434,8 @@ size_t zjni_compress_stream_batch_device(const void* d_src, const uint64_t* d_sr
 // last flush), or an error; 201 when the total exceeds the level's unknown-size window (the bundled library's stream takes over).
 size_t zjni_compress_stream(void* dst, size_t dstCap, const void* src, size_t srcSize, int level, int checksum, const uint32_t* flushAt, size_t nFlush, int final_, int knownEmpty) {
     if (level == 0) level = 3;
-    if (level < 1 || level > 3) return ZJNI_ERR(42);
-    if (srcSize > ((size_t)1 << ze_stream_window_log((u32)level)) || srcSize > ZE_MULTI_MAX) return ZJNI_ERR(201);
+    if (level > 3) return ZJNI_ERR(42);
+    if (srcSize > ((size_t)1 << ze_stream_window_log(level < 0 ? 1u : (u32)level)) || srcSize > ZE_MULTI_MAX) return ZJNI_ERR(201);     // (negative levels: level 1's 512 KiB window)
     if ((srcSize && !src) || (dstCap && !dst) || (nFlush && !flushAt) || nFlush > (1u << 20)) return ZJNI_ERR(72);
     DevState* d = cur_state();
     if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
@@ -2427,8 +2487,10 @@ size_t zjni_compress_batch_device_advanced(const void* d_src, const uint64_t* d_
 zjni_cdict* zjni_createCDict(const void* dict, size_t dictSize, int level) {
     DevState* d = cur_state();
     if (level == 0) level = 3;                        // ZSTD_createCDict: 0 = ZSTD_CLEVEL_DEFAULT
-    if (!d || !dict || dictSize < 8 || dictSize > 0x3FFFFFFFull || level < 1 || level > 3) return nullptr;
-    ZEParams const cp = ze_cdict_params((u32)level, (u32)dictSize);
+    if (!d || !dict || dictSize < 8 || dictSize > 0x3FFFFFFFull || level > 3) return nullptr;
+    level = zj_negative_word(level);                  // negative levels (zstd's --fast=N, clamped at ZSTD_minCLevel()): the CDict keeps their word, N included
+    bool const neg = ((u32)level & ZE_LW_NEG) != 0u;
+    ZEParams const cp = ze_cdict_params_of((u32)level, (u32)dictSize);
     size_t const head = (sizeof(ZECDictDev) + 15) & ~(size_t)15, tablesBytes = (size_t)ze_cdict_table_entries(cp) * 4u;
     zjni_cdict* cd = new zjni_cdict{t_dev, nullptr, 0, level, cp.strategy};
     if (hipMalloc(&cd->buf, head + tablesBytes + dictSize + 16) != hipSuccess) { delete cd; return nullptr; }
@@ -2438,7 +2500,7 @@ zjni_cdict* zjni_createCDict(const void* dict, size_t dictSize, int level) {
            && hipMemcpy(cd->buf, &hd, sizeof(hd), hipMemcpyHostToDevice) == hipSuccess
            && hipMemcpy(cd->buf + hd.rawOff, dict, dictSize, hipMemcpyHostToDevice) == hipSuccess;
     if (ok) {
-        hipLaunchKernelGGL(zj_cdict_digest_kernel, dim3(1), dim3(64), 0, 0, (u32)dictSize, (u32)level, (ZECDictDev*)cd->buf);
+        hipLaunchKernelGGL(neg ? zj_cdict_digest_kernel_neg : zj_cdict_digest_kernel, dim3(1), dim3(64), 0, 0, (u32)dictSize, (u32)level, (ZECDictDev*)cd->buf);
         ok = hipMemcpy(&hd, cd->buf, 64, hipMemcpyDeviceToHost) == hipSuccess && hd.status == 0;
     }
     if (!ok) { (void)hipFree(cd->buf); delete cd; return nullptr; }
@@ -2490,6 +2552,7 @@ size_t zjni_compress_batch_device_usingCDict(const void* d_src, const uint64_t* 
     size_t const fsB = sliceCap * (size_t)ZE_FRAME_STRIDE(ZC_MAX_SRC), metaB = (sliceCap * 12 + 255) & ~(size_t)255;
     u8* const tables = d->cdBuf;
     const ZECDictDev* const cd = (const ZECDictDev*)cdict->buf;
+    bool const neg = ((u32)cdict->level & ZE_LW_NEG) != 0u;     // a negative level: the two searches on their *_neg kernels (the entropy kernel takes the word as it is)
     unsigned long long* const eprof = d->prof ? d->prof + 16 : nullptr;
     int pending[2] = {0, 0};
     auto bail = [&](size_t code) {                       // an error mid-way still orders the caller's stream after the entropy kernels already posted
@@ -2511,7 +2574,7 @@ size_t zjni_compress_batch_device_usingCDict(const void* d_src, const uint64_t* 
         u32 const waves = (u32)((m + 63) / 64);
         u32 const gridM = waves < (u32)d->matchGrid ? waves : (u32)d->matchGrid;
         (void)hipEventRecord(d->tev[0], st);
-        hipLaunchKernelGGL(zj_enc_match_dict_kernel, dim3(gridM), dim3(64), 0, st, (const u8*)d_src, so, cd, (const u32*)list, (const u32*)ctr, ctr + 4, tables, fscratch, meta);
+        hipLaunchKernelGGL(neg ? zj_enc_match_dict_kernel_neg : zj_enc_match_dict_kernel, dim3(gridM), dim3(64), 0, st, (const u8*)d_src, so, cd, (const u32*)list, (const u32*)ctr, ctr + 4, tables, fscratch, meta);
         (void)hipEventRecord(d->tev[1], st); d->tevCompress = true;
         if (hipEventRecord(d->cdMatchDone[par], st) != hipSuccess || hipStreamWaitEvent(d->sideStream, d->cdMatchDone[par], 0) != hipSuccess) return bail(ZJNI_ERR(ZJNI_ERROR_no_device));
         u32 const gridA = (u32)(m < (size_t)d->encGridSmall ? m : (size_t)d->encGridSmall);
@@ -2528,7 +2591,7 @@ size_t zjni_compress_batch_device_usingCDict(const void* d_src, const uint64_t* 
         if (hipMemsetAsync(cc, 0, 8, st) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
         hipLaunchKernelGGL(zj_cdict_count_copy_kernel, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, (const u64*)d_src_off, (u32)n, cd, cc);
         u32 const gc = (u32)(n < (size_t)d->multiGrid ? n : (size_t)d->multiGrid);
-        hipLaunchKernelGGL(zj_encode_cdict_copy_kernel, dim3(gc), dim3(64), (u32)sizeof(ZEEntropy), st, (const u8*)d_src, (const u64*)d_src_off, (u8*)d_dst, (const u64*)d_dst_off,
+        hipLaunchKernelGGL(neg ? zj_encode_cdict_copy_kernel_neg : zj_encode_cdict_copy_kernel, dim3(gc), dim3(64), (u32)sizeof(ZEEntropy), st, (const u8*)d_src, (const u64*)d_src_off, (u8*)d_dst, (const u64*)d_dst_off,
                            (u64*)d_result, (u32)n, cd, (const u32*)cc, cc + 1, d->encScratch, d->multiTables, flags, (u32)sizeof(ZEEntropy));
     }
     return hipGetLastError() == hipSuccess ? 0 : ZJNI_ERR(ZJNI_ERROR_no_device);

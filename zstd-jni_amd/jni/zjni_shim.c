@@ -314,7 +314,7 @@ static void dict_register(JNIEnv* env, jobject obj, jfieldID field, void* gpu, i
 }
 static void* dict_digest(const void* bytes, size_t size, jint level, int compressSide) {
     if (!gpu_on()) return NULL;
-    if (compressSide) return (level >= 1 && level <= 3) ? (void*)zjni_createCDict(bytes, size, level) : NULL;
+    if (compressSide) return (level < 0 || (level >= 1 && level <= 3)) ? (void*)zjni_createCDict(bytes, size, level) : NULL;     /* levels 1-3 and every negative level */
     return (void*)zjni_createDDict(bytes, size);
 }
 JNIEXPORT void JNICALL P(ZstdDictCompress_init)(JNIEnv* env, jobject obj, jbyteArray dict, jint dict_offset, jint dict_size, jint level) {
@@ -437,7 +437,7 @@ static int gpu_takes_when(const CtxState* s, jint srcSize, int on) {
     if (s->rawDict && !s->localCdict && !s->cpuDict) {                 /* first compress after loadDict(byte[]): the local CDict, at the level of this moment */
         CtxState* w = (CtxState*)s;
         int const lvl = s->level == 0 ? 3 : s->level;
-        w->localCdict = (lvl >= 1 && lvl <= 3) ? zjni_createCDict(s->rawDict, s->rawDictSize, lvl) : NULL;
+        w->localCdict = lvl <= 3 ? zjni_createCDict(s->rawDict, s->rawDictSize, lvl) : NULL;      /* levels 1-3 and every negative level */
         if (!w->localCdict) w->cpuDict = 1;                            /* no digest (level > 3, under 8 bytes, refused): the bundled library has it */
         if (w->cpuDict) return 0;
     }
@@ -917,7 +917,7 @@ static void ss_forward_level(JNIEnv* env, StreamState* s) {
 }
 static void ss_next_frame(StreamState* s) {
     int const lv = s->hasLevelNext ? s->levelNext : s->level, ck = s->checksum, pc = s->paramCpu;
-    int const lc = s->hasLevelNext ? (lv < 0 || lv > 3) : s->levelCpu;
+    int const lc = s->hasLevelNext ? (lv > 3) : s->levelCpu;                      /* (every negative level is made here too) */
     ss_reset(s, lv); s->checksum = ck; s->levelCpu = lc; s->paramCpu = pc; s->hasLevelNext = 0;
     if (lc) s->cpuMode = 1;
 }
@@ -931,7 +931,7 @@ static int ss_note_parameter(jlong stream, int what, jint v) {       /* class Zs
         s->fwdLevel = v; s->fwdLevelPending = 1;
         return 2;
     }
-    if (what == 'l') { s->level = v == 0 ? 3 : v; s->levelCpu = (v < 0 || v > 3); if (s->levelCpu) s->cpuMode = 1; }
+    if (what == 'l') { s->level = v == 0 ? 3 : v; s->levelCpu = (v > 3); if (s->levelCpu) s->cpuMode = 1; }
     else if (what == 'k') s->checksum = (v & 0xFF) != 0;
     else { s->cpuMode = 1; s->paramCpu = 1; return 0; }
     return what == 'k' || !s->levelCpu;
@@ -945,7 +945,7 @@ static int streams_on_gpu(void) {
     }
     return state && gpu_on();
 }
-static size_t ss_window(int level) { return (size_t)1 << (18 + (level < 1 ? 3 : level)); }
+static size_t ss_window(int level) { return (size_t)1 << (18 + (level < 0 ? 1 : (level < 1 ? 3 : level))); }      /* negative levels: level 1's 512 KiB */
 static int ss_out_room(StreamState* s, size_t more) {
     if (s->outPos == s->outLen) s->outPos = s->outLen = 0;
     if (s->outLen + more > s->outCap) { size_t const c = (s->outLen + more) * 2 + 4096; unsigned char* p = (unsigned char*)realloc(s->out, c); if (!p) return 0; s->out = p; s->outCap = c; }
@@ -1033,8 +1033,8 @@ JNIEXPORT jlong JNICALL P(ZstdDirectBufferCompressingStreamNoFinalizer_initCStre
     jlong (*f)(JNIEnv*, jobject, jlong, jint) = (jlong (*)(JNIEnv*, jobject, jlong, jint))cpu_sym(PS("ZstdDirectBufferCompressingStreamNoFinalizer_initCStream"));
     StreamState* s = ss_get(stream, 1, 0);
     cs_fields(env, obj);
-    if (s) { ss_reset(s, level == 0 ? 3 : level); s->hasLevelNext = 0; if (level < 0 || level > 3 || !streams_on_gpu()) s->cpuMode = 1; }
-    if (!f && (level < 0 || level > 3)) return -(jlong)ZJNI_ERROR_unsupported;     /* no bundled library and a level this route does not make: said here, not at the first write */
+    if (s) { ss_reset(s, level == 0 ? 3 : level); s->hasLevelNext = 0; if (level > 3 || !streams_on_gpu()) s->cpuMode = 1; }
+    if (!f && level > 3) return -(jlong)ZJNI_ERROR_unsupported;     /* no bundled library and a level this route does not make: said here, not at the first write */
     return f ? f(env, obj, stream, level) : 0;
 }
 JNIEXPORT jlong JNICALL P(ZstdDirectBufferCompressingStreamNoFinalizer_initCStreamWithDict)(JNIEnv* env, jobject obj, jlong stream, jbyteArray dict, jint dict_size, jint level) {
@@ -1653,7 +1653,7 @@ static int cx_replay_to_cpu(JNIEnv* env, jclass cls, jlong ptr, StreamState* s) 
 }
 static int cx_plain(const CtxState* c) {                            /* what zjni_compress_stream can express: a level and the checksum flag */
     int const level = c->level == 0 ? 3 : c->level;
-    return !c->cpuOnly && !c->cpuDict && !c->cdict && !c->localCdict && !c->rawDict && !(c->hashLog | c->chainLog) && level >= 1 && level <= 3;
+    return !c->cpuOnly && !c->cpuDict && !c->cdict && !c->localCdict && !c->rawDict && !(c->hashLog | c->chainLog) && level <= 3;     /* levels 1-3 and every negative level */
 }
 /* One directive over raw memory: dst has `room` bytes free, src holds `n` unread bytes.  1: answered (*produced, *consumed, *done, or *err = a libzstd code);
  * 0: this frame is not for the GPU route and nothing has been touched — the caller passes the call on as it came. */
