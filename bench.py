@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — batched zstd compress + decompress on MI355X, BASELINE.json's metric and its named configs.
 
-  python bench.py --gpus N --steps K --warmup W [--config metric|1|2|3|4|5shape] [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--config metric|1|2|3|4|5shape] [--dump-outputs DIR] [--full]
   (N>1: launched by the driver through torch.distributed.run, one rank per GPU)
 
 config (config.workload names it in the JSON line):
@@ -16,6 +16,11 @@ config (config.workload names it in the JSON line):
 One step = one GPU pass of the config's direction(s) over the whole batch, inputs resident in HBM when the timed region
 starts.  At N>1 every rank runs the same per-GPU batch on different buffer indices (weak scaling) and the packed compressed
 output is gathered to rank 0 over RCCL inside the step.
+
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints its line: value, ms_per_step, the per-kernel HIP-event times of the
+timed steps, roofline and the GPU round-trip gate.  --full adds every leg outside the headline, each run after the timed steps: the level-3 passes
+with the LDS-sized tables (lds_tables_level3) and over a small batch (small_batch_level3), the gates against the reference (the rest of parity),
+cpu_baseline, end_to_end and --multi inprocess.  Without --full those fields are null.
 
 value        = uncompressed bytes through the config's pass per second, whole job.
 roofline     = dominant kernel's algorithmic bytes (S + C per buffer) / its HIP-event time, measured inside the library on the
@@ -81,13 +86,16 @@ def parse(argv=None):
     ap.add_argument("--verify-sample", type=int, default=512, help="GPU frames re-decoded / re-made by the CPU reference")
     ap.add_argument("--e2e-sample", type=int, default=65536, help="buffers in the end-to-end (host-pointer) leg (at most 4 GiB of them), 0 = skip")
     ap.add_argument("--no-gather", action="store_true", help="N>1: skip the RCCL gather of compressed output")
-    ap.add_argument("--skip-lds3", action="store_true", help="skip the extra level-3 pass with the LDS-sized tables (hashLog 14 / chainLog 13)")
+    ap.add_argument("--skip-lds3", action="store_true", help="--full: skip the extra level-3 passes (LDS-sized tables hashLog 14 / chainLog 13, the small batch)")
     ap.add_argument("--multi", default="", choices=["", "inprocess"], help="inprocess: also time zjni_compress_batch_multi / zjni_decompress_batch_multi (one process, a thread per visible GPU, host pointers) on a sample")
-    ap.add_argument("--skip-cpu", action="store_true", help="skip the CPU reference legs (verification + cpu_baseline + end_to_end), e.g. under a profiler")
+    ap.add_argument("--skip-cpu", action="store_true", help="--full: skip the CPU reference legs (verification + cpu_baseline + end_to_end), e.g. under a profiler")
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0; see dump_write)")
+    ap.add_argument("--full", action="store_true", help="also run the legs outside the headline (LDS-table and small-batch passes, reference gates, cpu_baseline, end_to_end, --multi)")
     a = ap.parse_args(argv)
     if a.steps < 1:
         ap.error("--steps must be at least 1")
+    if a.multi and not a.full:
+        ap.error("--multi is one of the --full legs")
     return a
 
 
@@ -382,7 +390,7 @@ def config5(a, zj, dev, rank, world, cfg):
                         break
             except OSError:
                 pass
-        if not a.skip_cpu and world == 1:
+        if a.full and not a.skip_cpu and world == 1:
             from oracle import ref
             k = 256
             hk = src[:k * size].cpu().numpy(); zs = csz[:k].cpu().tolist(); blob = comp[:k * bound].cpu().numpy()
@@ -602,10 +610,10 @@ def main(argv=None, platform_factory=GpuPlatform):
     route_kernel = L.zjni_route_kernel(route).decode() if route > 0 else ""
     stamp = L.zjni_build_stamp().decode() if P.native else "stand-in"
 
-    # ---- the LDS-sized level-3 tables (hashLog 14 / chainLog 13: round 2's default, now behind setHashLog / setChainLog), on the record every run:
+    # ---- the LDS-sized level-3 tables (hashLog 14 / chainLog 13: round 2's default, now behind setHashLog / setChainLog), on the record of every --full run:
     # one warm-up + a timed pass, outside `value`.  The headline itself runs the reference's own sizes (16 / 15).
     lds3 = None
-    if mode == "both" and level == 3 and size <= 65536 and not a.skip_lds3:
+    if a.full and mode == "both" and level == 3 and size <= 65536 and not a.skip_lds3:
         csz2 = torch.empty(n, dtype=torch.int64, device=dev)
         for it in range(2):
             p0, p1 = ev(), ev()
@@ -623,7 +631,7 @@ def main(argv=None, platform_factory=GpuPlatform):
     # buffers of the same batch, one warm-up + a timed call, outside `value`.  Below ZJNI_L3_WAVE_MAX frames the library sends every frame to a wave of its
     # own (zj_match_wavex.h on zj_encode_multi_kernel, route 9) instead of the lane pipeline, whose call costs ~95 ms whatever the batch size.
     small = None
-    if mode == "both" and level == 3 and size <= 131072 and n >= 1024 and not a.skip_lds3:
+    if a.full and mode == "both" and level == 3 and size <= 131072 and n >= 1024 and not a.skip_lds3:
         ns = 1024
         csz3 = torch.empty(ns, dtype=torch.int64, device=dev)
         for it in range(2):                              # frames go into `packed` (free after the timed steps): `comp` keeps the headline's frames for the gates
@@ -641,7 +649,7 @@ def main(argv=None, platform_factory=GpuPlatform):
     csum = int(csz.clamp(min=0).sum().item())
     cpu = None; e2e = None; multi = None
     gates = {"gpu_roundtrip_exact" if mode != "decode_ref" else "gpu_decodes_reference_frames_bit_exact": bool(roundtrip)}
-    if rank == 0 and not a.skip_cpu:
+    if rank == 0 and a.full and not a.skip_cpu:
         from oracle import port, ref
         assert ref.available(), "oracle/_ref/libzstd_ref.so missing: run __graft_entry__.build() where /root/reference exists"
         k = min(a.verify_sample, n, max(8, (64 << 20) // size))

@@ -56,6 +56,26 @@ def test_bench_dump_outputs_and_steps(tmp_path, capsys, monkeypatch):
         assert B.util.emu_decompress(B.L, f, size) == raw[i].tobytes()
 
 
+def test_plain_run_is_the_warm_up_and_the_timed_steps(capsys, monkeypatch):
+    """without --full and without any --skip-* option, a level-3 run of the metric's mode does nothing beyond its headline: no LDS-table pass, no
+    reference gates, no CPU or end-to-end legs (those fields null), the GPU round trip still checked"""
+    for v in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        monkeypatch.delenv(v, raising=False)
+    steps = 2
+    j, B = _run(["--gpus", "1", "--steps", str(steps), "--warmup", "1", "--buffers", "4", "--size", "4096", "--level", "3"], capsys)
+    assert B.calls == {"compress": 1 + steps, "pack": 1 + steps, "decompress": 1 + steps}
+    assert j["steps"] == steps and j["config"]["level"] == 3 and j["config"]["value_is"] == "both"
+    assert all(j[k] is None for k in ("lds_tables_level3", "small_batch_level3", "cpu_baseline", "end_to_end", "multi_inprocess"))
+    assert j["parity"] == {"gpu_roundtrip_exact": True}
+
+
+def test_full_is_off_by_default_and_carries_multi():
+    assert bench.parse([]).full is False and bench.parse(["--full"]).full is True
+    assert bench.parse(["--full", "--multi", "inprocess"]).multi == "inprocess"
+    with pytest.raises(SystemExit):
+        bench.parse(["--multi", "inprocess"])
+
+
 def test_bench_refuses_zero_steps():
     with pytest.raises(SystemExit):
         bench.parse(["--steps", "0"])

@@ -6,7 +6,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}; OUT=$R/gpurun_out/r03final; mkdir -p $OUT
 cd $R
 for C in metric 3 2 4 1 5shape; do
-  timeout 240 python bench.py --config $C --steps 5 --warmup 2 > $OUT/bench_config$C.json 2> $OUT/bench_config$C.err
+  timeout 240 python bench.py --config $C --steps 5 --warmup 2 --full > $OUT/bench_config$C.json 2> $OUT/bench_config$C.err
   python - <<PY
 import json
 try:
@@ -16,5 +16,5 @@ try:
 except Exception as ex: print("$C FAILED", ex)
 PY
 done
-timeout 300 python bench.py --config 5 --buffers 131072 --steps 2 --warmup 1 > $OUT/bench_config5_two_chunks.json 2> $OUT/bench_config5.err; tail -c 300 $OUT/bench_config5_two_chunks.json | head -c 300; echo
+timeout 300 python bench.py --config 5 --buffers 131072 --steps 2 --warmup 1 --full > $OUT/bench_config5_two_chunks.json 2> $OUT/bench_config5.err; tail -c 300 $OUT/bench_config5_two_chunks.json | head -c 300; echo
 PMC_LIST=$'metric 3 65536 65536 ZJNI_NEED_INLINE=1\nmetricnoflags 3 65536 65536 ZJNI_NEED=0\n3 1 65536 65536' bash tools/pmc_traffic.sh r03final 2>&1 | tail -8
