@@ -97,6 +97,41 @@ size_t zjni_compress_batch_device2(const void* d_src, const uint64_t* d_src_off,
                                    void* d_dst, const uint64_t* d_dst_off,
                                    uint64_t* d_result, size_t n, int level, int checksum, void* stream);
 
+/* ---- sizing a decompress batch from its frames alone ----
+ * A consumer that holds frames only (the root of the multi-GPU gather, frames read from storage or a peer straight into HBM) does not know
+ * d_dst_off.  The entries below take a buffer of concatenated zstd and skippable frames and answer what the reference's header-only calls
+ * answer for it, for every input, valid or not; nothing outside [src, src + srcSize) is read.  Legacy formats are off, as in the bundled build. */
+typedef struct zjni_frame_info {   /* 40 bytes, 8-aligned, same layout on host and device */
+    uint64_t content;         /* ZSTD_findDecompressedSize(buf): sum over all frames; ~0 unknown, ~0 - 1 error */
+    uint64_t bound;           /* ZSTD_decompressBound(buf); ~0 - 1 error */
+    uint64_t firstFrameSize;  /* ZSTD_findFrameCompressedSize(buf): bytes of the first (zstd or skippable) frame,
+                                 or the reference's own error code in the size_t convention */
+    uint32_t dictID;          /* ZSTD_getDictID_fromFrame(buf) */
+    uint32_t frames;          /* complete zstd frames walked before the end or the first malformed spot */
+    uint32_t skippable;       /* complete skippable frames, likewise */
+    uint32_t flags;           /* ZJNI_INFO_* over the frames counted above */
+} zjni_frame_info;
+#define ZJNI_INFO_CHECKSUM 1u   /* some zstd frame carries a checksum */
+#define ZJNI_INFO_UNKNOWN  2u   /* some zstd frame has no content size */
+#define ZJNI_INFO_SINGLE   4u   /* exactly one zstd frame filling the buffer, nothing else */
+/* Replaces ZSTD_findDecompressedSize + ZSTD_decompressBound + ZSTD_findFrameCompressedSize + ZSTD_getDictID_fromFrame
+ * (N/decompress/zstd_decompress.c:643-680, :820-836, :809-812, :1644-1650) for one buffer, in one walk over its frame and block
+ * headers.  Runs on the host and needs no device, like zjni_getFrameContentSize.  Returns 0. */
+size_t zjni_inspect(const void* src, size_t srcSize, zjni_frame_info* out);
+/* The same four calls for n buffers in HBM (layout below: buffer i = d_src[d_src_off[i] .. d_src_off[i + 1])), one lane per buffer:
+ * d_info[i] = what zjni_inspect answers for buffer i.  Replaces a copy of every header to the host, one ZSTD_getFrameContentSize /
+ * ZSTD_findFrameCompressedSize per frame there (N/jni_zstd.c:116-130) and an upload of the sizes.  Asynchronous on `stream`. */
+size_t zjni_inspect_batch_device(const void* d_src, const uint64_t* d_src_off, zjni_frame_info* d_info, size_t n, void* stream);
+/* d_dst_off[0 .. n] for a decompress call, from d_info[0 .. n): replaces the host loop that sums ZSTD_getFrameContentSize /
+ * ZSTD_decompressBound results into destination offsets.  Buffer i's slot is its `content` when known, else its `bound` when that is not
+ * the error value, else 0; with slotMax != 0 a slot above slotMax counts as 0 (one hostile header declaring 2^60 bytes would starve every
+ * buffer behind it); slots are rounded up to `align`, a power of two from 1 to 65536 (anything else: ZSTD_error_parameter_outOfBound).
+ * d_needed[0] = the sum of all slots; d_dst_off[k] = min(sum of slots 0 .. k - 1, dstCapacity): buffers that do not fit get a short or
+ * empty slot, the decoder answers ZSTD_error_dstSize_tooSmall for them by itself, and the caller compares d_needed[0] with its capacity
+ * and retries.  Sums saturate at 2^64 - 1.  n == 0 is legal.  Asynchronous on `stream`. */
+size_t zjni_decompress_offsets_device(const zjni_frame_info* d_info, size_t n, uint64_t dstCapacity, uint64_t align, uint64_t slotMax,
+                                      uint64_t* d_dst_off, uint64_t* d_needed, void* stream);
+
 /* ---- dictionaries, decompress side (SURVEY.md §8a last rows; BASELINE config 4) ----
  * zjni_ddict == ZSTD_DDict as zstd-jni holds it in ZstdDictDecompress.nativePtr (J/ZstdDictDecompress.java,
  * N/jni_fast_zstd.c:56-96): created once from the dictionary bytes (zstd dictionary format with magic
@@ -116,6 +151,15 @@ size_t zjni_decompress_batch_usingDDict(const void* const* src, const size_t* sr
                                         void* const* dst, const size_t* dstCapacity,
                                         size_t* result, size_t n, const zjni_ddict* ddict);
 size_t zjni_decompress_usingDDict(void* dst, size_t dstCapacity, const void* src, size_t srcSize, const zjni_ddict* ddict);
+/* zjni_inspect_batch_device + zjni_decompress_offsets_device + zjni_decompress_batch_device_usingDDict in one call, nothing waited for on the
+ * host: replaces ZSTD_findDecompressedSize / ZSTD_decompressBound per buffer on the host (N/decompress/zstd_decompress.c:643-680, :820-836)
+ * followed by ZSTD_decompress_usingDDict (N/jni_fast_zstd.c:133-183) for n buffers whose decoded sizes the caller does not know.  d_info[n],
+ * d_dst_off[n + 1] and d_needed[1] are outputs; d_result and the bytes under d_dst are those of zjni_decompress_batch_device_usingDDict called
+ * with the offsets this call wrote.  A d_needed[0] above dstCapacity says which capacity a second call needs; buffers that did fit are decoded
+ * already.  Ordered with the device's other batch calls like every batch entry.  n == 0 is legal: d_dst_off[0] = 0, d_needed[0] = 0. */
+size_t zjni_decompress_batch_device_sized(const void* d_src, const uint64_t* d_src_off, void* d_dst, uint64_t dstCapacity, uint64_t align,
+                                          uint64_t slotMax, zjni_frame_info* d_info, uint64_t* d_dst_off, uint64_t* d_needed,
+                                          uint64_t* d_result, size_t n, const zjni_ddict* ddict, void* stream);
 
 /* ---- explicit table sizes: ZstdCompressCtx.setHashLog / setChainLog (J/ZstdCompressCtx.java; N/jni_fast_zstd.c setHashLog0 /
  * setChainLog0 -> ZSTD_c_hashLog / ZSTD_c_chainLog) on top of level + checksum; 0 = not set.  Honoured for level 3

@@ -30,6 +30,15 @@ ERR_UNSUPPORTED = 201
 _lib = None
 
 
+class FrameInfo(C.Structure):
+    """zjni_frame_info (include/zjni_amd.h): what a buffer of concatenated frames decodes to, from its headers alone."""
+    _fields_ = [("content", C.c_uint64), ("bound", C.c_uint64), ("firstFrameSize", C.c_uint64),
+                ("dictID", C.c_uint32), ("frames", C.c_uint32), ("skippable", C.c_uint32), ("flags", C.c_uint32)]
+
+
+INFO_CHECKSUM, INFO_UNKNOWN, INFO_SINGLE = 1, 2, 4
+
+
 def build_stamp():
     """What the library is built from: a hash of csrc/ and the header (the GPU box has no .git, and a revision says nothing about
     uncommitted edits): profiles/ and roofline.traffic are stamped with it (zjni_build_stamp)."""
@@ -193,6 +202,15 @@ def lib():
     L.zjni_compress_stream.argtypes = [vp, sz, vp, sz, C.c_int, C.c_int, vp, sz, C.c_int, C.c_int]
     L.zjni_compress_stream_batch_device.restype = sz
     L.zjni_compress_stream_batch_device.argtypes = [vp, vp, vp, vp, vp, sz, C.c_int, C.c_int, vp, vp, vp, vp]
+    if hasattr(L, "zjni_inspect"):                       # (absent from older variant libraries loaded through ZJNI_LIB for A/B runs, like zjni_last_decode_lists2)
+        L.zjni_inspect.restype = sz
+        L.zjni_inspect.argtypes = [vp, sz, vp]
+        L.zjni_inspect_batch_device.restype = sz
+        L.zjni_inspect_batch_device.argtypes = [vp, vp, vp, sz, vp]
+        L.zjni_decompress_offsets_device.restype = sz
+        L.zjni_decompress_offsets_device.argtypes = [vp, sz, C.c_uint64, C.c_uint64, C.c_uint64, vp, vp, vp]
+        L.zjni_decompress_batch_device_sized.restype = sz
+        L.zjni_decompress_batch_device_sized.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, vp, vp, vp, vp, sz, vp, vp]
     _lib = L
     return L
 
@@ -211,7 +229,8 @@ EXPORTS = ("zjni_version", "zjni_device_count", "zjni_init", "zjni_shutdown", "z
            "zjni_compress_batch_device_advanced", "zjni_compress_batch_advanced",
            "zjni_createAggregator", "zjni_freeAggregator", "zjni_aggregator_compress", "zjni_aggregator_decompress", "zjni_aggregator_stats",
            "zjni_last_route", "zjni_route_kernel", "zjni_build_stamp", "zjni_compress_stream", "zjni_compress_stream_batch_device", "zjni_frame_extent", "zjni_last_lists", "zjni_last_decode_lists", "zjni_last_decode_lists2",
-           "zjni_compress_batch_begin", "zjni_decompress_batch_begin", "zjni_batch_finish", "zjni_pack_batch_device2")
+           "zjni_compress_batch_begin", "zjni_decompress_batch_begin", "zjni_batch_finish", "zjni_pack_batch_device2",
+           "zjni_inspect", "zjni_inspect_batch_device", "zjni_decompress_offsets_device", "zjni_decompress_batch_device_sized")
 
 
 # --------------------------------------------------------------------------- Java API mirror --
@@ -643,6 +662,16 @@ def _host_batch(srcs, caps, is_compress, level, checksum=False, dictionary=None,
             out.append(ZstdException(res[i]))
         else:
             out.append(outs[i].raw[:res[i]])
+    return out
+
+
+def inspect(data):
+    """zjni_inspect on host bytes: a FrameInfo (ZSTD_findDecompressedSize, ZSTD_decompressBound, ZSTD_findFrameCompressedSize and
+    ZSTD_getDictID_fromFrame of `data` in one walk; no device needed).  The walk is given an exact-size copy of the bytes."""
+    data = bytes(data)
+    buf = (C.c_ubyte * len(data)).from_buffer_copy(data) if data else None
+    out = FrameInfo()
+    lib().zjni_inspect(buf, len(data), C.byref(out))
     return out
 
 

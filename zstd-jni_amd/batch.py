@@ -72,6 +72,68 @@ def decompress(src_blob, src_off, dst_blob, dst_off, results=None, dictionary=No
     return results
 
 
+class BatchInfo:
+    """zjni_frame_info per buffer as tensors: content / bound / first_frame_size int64[n] (-1 unknown, -2 error, a negative ZSTD error code
+    for first_frame_size: the values read as signed, as elsewhere), dict_id / frames / skippable / flags int64[n].  `raw` is the
+    int64[n, 5] image of the device's zjni_frame_info[n] the fields are views of or made from."""
+
+    def __init__(self, raw):
+        self.raw = raw
+        self.content, self.bound, self.first_frame_size = raw[:, 0], raw[:, 1], raw[:, 2]
+        self.dict_id, self.frames = raw[:, 3] & 0xFFFFFFFF, (raw[:, 3] >> 32) & 0xFFFFFFFF
+        self.skippable, self.flags = raw[:, 4] & 0xFFFFFFFF, (raw[:, 4] >> 32) & 0xFFFFFFFF
+
+
+def inspect(src_blob, src_off):
+    """Enqueue zjni_inspect_batch_device on the current stream: what every buffer of concatenated frames decodes to, from its headers
+    alone (ZSTD_findDecompressedSize, ZSTD_decompressBound, ZSTD_findFrameCompressedSize, ZSTD_getDictID_fromFrame).  Returns a BatchInfo."""
+    n = src_off.numel() - 1
+    raw = torch.empty((n, 5), dtype=torch.int64, device=src_blob.device)
+    _check(lib().zjni_inspect_batch_device(src_blob.data_ptr(), src_off.data_ptr(), raw.data_ptr(), n, _stream_ptr()))
+    return BatchInfo(raw)
+
+
+def decompress_offsets(info, capacity=None, align=1, slot_max=0, dst_off=None, needed=None):
+    """Enqueue zjni_decompress_offsets_device: (dst_off int64[n + 1], needed int64[1]) from a BatchInfo.  capacity None = unlimited."""
+    n = info.raw.shape[0]
+    if dst_off is None:
+        dst_off = torch.empty(n + 1, dtype=torch.int64, device=info.raw.device)
+    if needed is None:
+        needed = torch.empty(1, dtype=torch.int64, device=info.raw.device)
+    cap = (1 << 64) - 1 if capacity is None else capacity
+    _check(lib().zjni_decompress_offsets_device(info.raw.data_ptr(), n, cap, align, slot_max, dst_off.data_ptr(), needed.data_ptr(), _stream_ptr()))
+    return dst_off, needed
+
+
+def decompress_sized(src_blob, src_off, dst_blob=None, dictionary=None, align=1, slot_max=0):
+    """Decompress a batch whose decoded sizes the caller does not know: returns (dst_blob, dst_off int64[n + 1], results int64[n], needed).
+    With a `dst_blob` (uint8) it is one library call (zjni_decompress_batch_device_sized) and nothing synchronises with the host: `needed`
+    is an int64[1] tensor, to be compared with dst_blob.numel() when the results are read — buffers that did not fit report -70.
+    Without one the batch is inspected, the offsets computed, `needed` read (the only host wait; returned as an int), the blob allocated
+    and the existing decompress() called.  Frames without a content size land in slots of their bound; pack(results, dst_blob, dst_off)
+    compacts them."""
+    n = src_off.numel() - 1
+    dev = src_blob.device
+    dd = dictionary._ptr if dictionary is not None else None
+    if dst_blob is not None:
+        if dst_blob.dtype != torch.uint8 or not dst_blob.is_contiguous():
+            raise ValueError("decompress_sized: dst_blob must be a contiguous uint8 tensor")
+        raw = torch.empty((n, 5), dtype=torch.int64, device=dev)
+        dst_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        needed = torch.empty(1, dtype=torch.int64, device=dev)
+        results = torch.empty(n, dtype=torch.int64, device=dev)
+        _check(lib().zjni_decompress_batch_device_sized(src_blob.data_ptr(), src_off.data_ptr(), dst_blob.data_ptr(), dst_blob.numel(), align, slot_max,
+                                                        raw.data_ptr(), dst_off.data_ptr(), needed.data_ptr(), results.data_ptr(), n, dd, _stream_ptr()))
+        return dst_blob, dst_off, results, needed
+    dst_off, needed = decompress_offsets(inspect(src_blob, src_off), None, align, slot_max)
+    total = int(needed.item())
+    if total < 0:
+        raise ZstdException(64, "decompress_sized: the batch declares more than 2^63 bytes; set slot_max")
+    dst_blob = torch.empty(max(total, 1), dtype=torch.uint8, device=dev)[:total]
+    results = decompress(src_blob, src_off, dst_blob, dst_off, dictionary=dictionary)
+    return dst_blob, dst_off, results, total
+
+
 def pack(results, dst_blob, dst_off, out=None, out_off=None):
     """Tightly pack a compress batch's variable-size outputs (sizes = results) into one blob:
     returns (packed_blob, packed_off int64[n+1]).  With `out` (uint8, capacity >= sum of sizes) and `out_off`

@@ -30,6 +30,7 @@
 #endif
 #include "zj_match_wave.h"
 #include "zj_synth.h"
+#include "zj_frameinfo.h"
 
 #define ZJNI_ERR(code) ((size_t)0 - (size_t)(code))
 
@@ -1249,6 +1250,7 @@ struct DevState {
     u8* dsplitBuf = nullptr; size_t dsplitBufCap = 0;  // [tables][sequences][frame records][list A][list B]
     u8* dlitBuf = nullptr; size_t dlitBufCap = 0;      // literal slots of the split decode pipeline (stage 2b), one per frame of a slice
     u8* dmbBuf = nullptr; size_t dmbBufCap = 0;        // multi-block frames on the split pipeline: [block tables][blocks][frames][seq list][list M][record pool]
+    u64* slotPart = nullptr; size_t slotPartCap = 0;   // zjni_decompress_offsets_device: one partial sum per 1 024 buffers (8 B each; not counted as pipeline scratch)
 };
 std::mutex g_mu;        // guards g_dev
 std::vector<DevState> g_dev;
@@ -1461,6 +1463,7 @@ void zjni_shutdown(void) {
         if (d.multiTables) (void)hipFree(d.multiTables);
         if (d.cdBuf) (void)hipFree(d.cdBuf);
         if (d.cdList) (void)hipFree(d.cdList);
+        if (d.slotPart) (void)hipFree(d.slotPart);
         for (int p = 0; p < 2; p++) { if (d.cdMatchDone[p]) (void)hipEventDestroy(d.cdMatchDone[p]); if (d.cdEncDone[p]) (void)hipEventDestroy(d.cdEncDone[p]); }
         if (d.sideStream) { (void)hipStreamDestroy(d.sideStream); (void)hipEventDestroy(d.evFork); (void)hipEventDestroy(d.evJoin); }
         if (d.clearStream) { (void)hipStreamDestroy(d.clearStream); (void)hipEventDestroy(d.evMatchDone); (void)hipEventDestroy(d.evCleared); }
@@ -1877,9 +1880,16 @@ struct BatchOrder {
     }
     ~BatchOrder() { if (!d) return; d->lastValid = (hipEventRecord(d->lastDone, st) == hipSuccess); d->enqueueMu->unlock(); }
 };
+static size_t decompress_chunked_ordered(const void* d_src, const uint64_t* d_src_off, void* d_dst, const uint64_t* d_dst_off,
+                                         uint64_t* d_result, size_t n, const zjni_ddict* ddict, void* stream);
 static size_t decompress_chunked(const void* d_src, const uint64_t* d_src_off, void* d_dst, const uint64_t* d_dst_off,
                                  uint64_t* d_result, size_t n, const zjni_ddict* ddict, void* stream) {
     BatchOrder order(cur_state(), stream);
+    return decompress_chunked_ordered(d_src, d_src_off, d_dst, d_dst_off, d_result, n, ddict, stream);
+}
+// (the caller holds the device's BatchOrder)
+static size_t decompress_chunked_ordered(const void* d_src, const uint64_t* d_src_off, void* d_dst, const uint64_t* d_dst_off,
+                                         uint64_t* d_result, size_t n, const zjni_ddict* ddict, void* stream) {
     size_t const chunk = scratch_slice((size_t)ZD_SPLIT_TAB_BYTES + ZD_SPLIT_SEQ_BYTES + sizeof(ZDMeta) + 8, ZJ_CHUNK_FRAMES, 1);
     for (size_t at = 0; at < n || at == 0; at += chunk) {
         size_t const m = n - at < chunk ? n - at : chunk;
@@ -1896,6 +1906,141 @@ size_t zjni_decompress_batch_device_usingDDict(const void* d_src, const uint64_t
                                                uint64_t* d_result, size_t n, const zjni_ddict* ddict, void* stream) {
     if (ddict && ddict->ordinal != t_dev && t_dev >= 0) return ZJNI_ERR(32);      // digested on another device
     return decompress_chunked(d_src, d_src_off, d_dst, d_dst_off, d_result, n, ddict, stream);
+}
+
+// ---- sizing a decompress batch from its frames alone (zj_frameinfo.h) ----
+size_t zjni_inspect(const void* src, size_t srcSize, zjni_frame_info* out) {
+    zj_frame_walk((const u8*)src, src ? (u64)srcSize : 0, out);
+    return 0;
+}
+// One lane per buffer: the walk is a chain of dependent block-header reads, nothing for a wave to share.  Workgroups of one wave and no barrier, so a frame
+// of many blocks keeps back the 63 buffers of its own wave and nobody else's.
+__global__ __launch_bounds__(64) void zj_inspect_kernel(const u8* __restrict__ src, const u64* __restrict__ off, zjni_frame_info* __restrict__ info, u32 n) {
+    u64 const i = (u64)blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    u64 const lo = off[i], hi = off[i + 1];
+    zjni_frame_info fi;
+    zj_frame_walk(src + lo, hi > lo ? hi - lo : 0, &fi);
+    info[i] = fi;
+}
+// The offsets are a scan over n slots in three launches: every workgroup of 256 lanes takes 1 024 buffers (4 neighbours per lane), writes their slots to
+// off[1 + i] and their sum to part[workgroup]; one workgroup scans the partial sums (n / 1 024 of them); the first kernel's grid again turns the slots into
+// clamped prefix sums in place.  Additions saturate (zj_sat_add: associative, so the order of the tree does not show).
+#define ZJ_SLOT_WG 256u
+#define ZJ_SLOT_PER_WG 1024u
+// exclusive prefix of v over the workgroup's 256 lanes, *total = their sum (Hillis-Steele in LDS)
+__device__ __forceinline__ u64 zj_slot_scan256(u64 v, u64* sh, u64* total) {
+    u32 const t = threadIdx.x;
+    sh[t] = v;
+    __syncthreads();
+    for (u32 d = 1; d < ZJ_SLOT_WG; d <<= 1) {
+        u64 const w = t >= d ? sh[t - d] : 0;
+        __syncthreads();
+        sh[t] = zj_sat_add(sh[t], w);
+        __syncthreads();
+    }
+    u64 const excl = t ? sh[t - 1] : 0;
+    *total = sh[ZJ_SLOT_WG - 1];
+    __syncthreads();
+    return excl;
+}
+__global__ __launch_bounds__(ZJ_SLOT_WG) void zj_slot_sizes_kernel(const zjni_frame_info* __restrict__ info, u64 n, u64 alignMask, u64 slotMax,
+                                                                   u64* __restrict__ off, u64* __restrict__ part) {
+    __shared__ u64 sh[ZJ_SLOT_WG];
+    u64 const base = (u64)blockIdx.x * ZJ_SLOT_PER_WG + (u64)threadIdx.x * 4u;
+    u64 sum = 0;
+    for (u32 k = 0; k < 4; k++) {
+        u64 const i = base + k;
+        if (i >= n) break;
+        u64 const slot = zj_info_slot(info[i].content, info[i].bound, alignMask, slotMax);
+        off[i + 1] = slot;
+        sum = zj_sat_add(sum, slot);
+    }
+    u64 total;
+    (void)zj_slot_scan256(sum, sh, &total);
+    if (threadIdx.x == 0) part[blockIdx.x] = total;
+}
+// part[0 .. m) -> its exclusive prefix sums in place, needed[0] = the total, off[0] = 0: one workgroup, a contiguous run per lane (zj_pack_offsets_kernel's shape)
+__global__ __launch_bounds__(1024) void zj_slot_parts_kernel(u64* __restrict__ part, u64 m, u64* __restrict__ needed, u64* __restrict__ off) {
+    __shared__ u64 sh[1024];
+    u32 const t = threadIdx.x;
+    u64 const per = (m + 1023u) / 1024u, lo0 = (u64)t * per, lo = lo0 < m ? lo0 : m, hi = lo + per < m ? lo + per : m;
+    u64 sum = 0;
+    for (u64 i = lo; i < hi; i++) sum = zj_sat_add(sum, part[i]);
+    sh[t] = sum;
+    __syncthreads();
+    for (u32 d = 1; d < 1024u; d <<= 1) {
+        u64 const v = t >= d ? sh[t - d] : 0;
+        __syncthreads();
+        sh[t] = zj_sat_add(sh[t], v);
+        __syncthreads();
+    }
+    u64 run = t ? sh[t - 1] : 0;
+    for (u64 i = lo; i < hi; i++) { u64 const z = part[i]; part[i] = run; run = zj_sat_add(run, z); }
+    if (t == 1023u) { needed[0] = sh[1023]; off[0] = 0; }
+}
+__global__ __launch_bounds__(ZJ_SLOT_WG) void zj_slot_offsets_kernel(u64* __restrict__ off, u64 n, u64 cap, const u64* __restrict__ part) {
+    __shared__ u64 sh[ZJ_SLOT_WG];
+    u64 const base = (u64)blockIdx.x * ZJ_SLOT_PER_WG + (u64)threadIdx.x * 4u;
+    u64 slot[4], sum = 0;
+    for (u32 k = 0; k < 4; k++) { slot[k] = base + k < n ? off[base + k + 1] : 0; sum = zj_sat_add(sum, slot[k]); }
+    u64 total;
+    u64 run = zj_sat_add(part[blockIdx.x], zj_slot_scan256(sum, sh, &total));
+    for (u32 k = 0; k < 4; k++) {
+        if (base + k >= n) break;
+        run = zj_sat_add(run, slot[k]);
+        off[base + k + 1] = run < cap ? run : cap;
+    }
+}
+static bool slot_align_ok(u64 align) { return align >= 1 && align <= 65536 && (align & (align - 1)) == 0; }
+// (the caller holds the device's BatchOrder: `slotPart` is shared by the device's calls)
+static size_t inspect_enqueue(DevState* d, const void* d_src, const uint64_t* d_src_off, zjni_frame_info* d_info, size_t n, hipStream_t st) {
+    if (n == 0) return 0;
+    if (n > 0xFFFFFFFFull) return ZJNI_ERR(72);
+    hipLaunchKernelGGL(zj_inspect_kernel, dim3((u32)((n + 63) / 64)), dim3(64), 0, st, (const u8*)d_src, (const u64*)d_src_off, d_info, (u32)n);
+    return hipGetLastError() == hipSuccess ? 0 : ZJNI_ERR(ZJNI_ERROR_no_device);
+}
+static size_t offsets_enqueue(DevState* d, const zjni_frame_info* d_info, size_t n, u64 cap, u64 align, u64 slotMax, u64* d_dst_off, u64* d_needed, hipStream_t st) {
+    if (n > 0xFFFFFFFFull) return ZJNI_ERR(72);
+    if (n == 0) return hipMemsetAsync(d_dst_off, 0, 8, st) == hipSuccess && hipMemsetAsync(d_needed, 0, 8, st) == hipSuccess ? 0 : ZJNI_ERR(ZJNI_ERROR_no_device);
+    size_t const groups = (n + ZJ_SLOT_PER_WG - 1) / ZJ_SLOT_PER_WG;
+    if (groups > d->slotPartCap) {
+        size_t const want = groups < 8192 ? 8192 : groups;
+        if (d->slotPart) (void)hipFree(d->slotPart);          // (drains the device: an earlier call may still be reading it)
+        d->slotPart = nullptr; d->slotPartCap = 0;
+        if (hipMalloc(&d->slotPart, want * 8) != hipSuccess) return ZJNI_ERR(64);
+        d->slotPartCap = want;
+    }
+    hipLaunchKernelGGL(zj_slot_sizes_kernel, dim3((u32)groups), dim3(ZJ_SLOT_WG), 0, st, d_info, (u64)n, align - 1, slotMax, d_dst_off, d->slotPart);
+    hipLaunchKernelGGL(zj_slot_parts_kernel, dim3(1), dim3(1024), 0, st, d->slotPart, (u64)groups, d_needed, d_dst_off);
+    hipLaunchKernelGGL(zj_slot_offsets_kernel, dim3((u32)groups), dim3(ZJ_SLOT_WG), 0, st, d_dst_off, (u64)n, cap, (const u64*)d->slotPart);
+    return hipGetLastError() == hipSuccess ? 0 : ZJNI_ERR(ZJNI_ERROR_no_device);
+}
+size_t zjni_inspect_batch_device(const void* d_src, const uint64_t* d_src_off, zjni_frame_info* d_info, size_t n, void* stream) {
+    DevState* d = cur_state();
+    if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    return inspect_enqueue(d, d_src, d_src_off, d_info, n, (hipStream_t)stream);      // no shared scratch: needs no place in the device's order
+}
+size_t zjni_decompress_offsets_device(const zjni_frame_info* d_info, size_t n, uint64_t dstCapacity, uint64_t align, uint64_t slotMax,
+                                      uint64_t* d_dst_off, uint64_t* d_needed, void* stream) {
+    if (!slot_align_ok(align)) return ZJNI_ERR(42);
+    DevState* d = cur_state();
+    if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    BatchOrder order(d, stream);
+    return offsets_enqueue(d, d_info, n, dstCapacity, align, slotMax, d_dst_off, d_needed, (hipStream_t)stream);
+}
+size_t zjni_decompress_batch_device_sized(const void* d_src, const uint64_t* d_src_off, void* d_dst, uint64_t dstCapacity, uint64_t align,
+                                          uint64_t slotMax, zjni_frame_info* d_info, uint64_t* d_dst_off, uint64_t* d_needed,
+                                          uint64_t* d_result, size_t n, const zjni_ddict* ddict, void* stream) {
+    if (!slot_align_ok(align)) return ZJNI_ERR(42);
+    if (ddict && ddict->ordinal != t_dev && t_dev >= 0) return ZJNI_ERR(32);      // digested on another device
+    DevState* d = cur_state();
+    if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    BatchOrder order(d, stream);
+    size_t r = inspect_enqueue(d, d_src, d_src_off, d_info, n, (hipStream_t)stream);
+    if (r == 0) r = offsets_enqueue(d, d_info, n, dstCapacity, align, slotMax, d_dst_off, d_needed, (hipStream_t)stream);
+    if (r != 0) return r;
+    return decompress_chunked_ordered(d_src, d_src_off, d_dst, d_dst_off, d_result, n, ddict, stream);
 }
 
 // ZSTD_createDDict (N/decompress/zstd_ddict.c:36-130; ZstdDictDecompress.init, N/jni_fast_zstd.c:56-75): the raw
