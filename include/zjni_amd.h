@@ -204,6 +204,41 @@ size_t zjni_compress_stream_batch_device(const void* d_src, const uint64_t* d_sr
                                          uint64_t* d_result, size_t n, int level, int checksum,
                                          const uint32_t* d_flush_at, const uint64_t* d_flush_off, const uint32_t* d_mode, void* stream);
 
+/* ---- stream frames continued from device state ----
+ * Replaces ZSTD_compressStream2 with ZSTD_e_flush / ZSTD_e_end on a LIVE ZSTD_CStream (N/compress/zstd_compress.c:6103-6300): the entries above keep nothing
+ * between calls, so every flush compresses the stream again from its first byte and returns the frame's beginning again.  Here the stream's state — its hash
+ * table(s), the repcodes and the Huffman table of the last compressed block, what it has consumed and produced — stays in device memory between calls: a call
+ * compresses only the bytes written since the last flush and returns only the frame's NEW bytes.  The calls' outputs, concatenated, are the frame the entries
+ * above write for the whole stream, byte for byte; the levels, the windows and the buffering until a flush are theirs.
+ *
+ * Device form.  zjni_cstream_state_bytes(level): bytes of one stream's state, a multiple of 256 (0: a level the streams do not serve); the caller owns the
+ * memory, state i lies at d_state + i * zjni_cstream_state_bytes(level), and an all-zero state (a memset) is a stream on which nothing has been done.
+ * zjni_compress_stream_continue_batch_device takes zjni_compress_stream_batch_device's arguments plus d_state: d_src slot i holds EVERYTHING written to stream i
+ * so far, d_dst slot i receives the new frame bytes only, d_result[i] is their count — 0 when nothing was flushed since the last call.  Flush positions at or
+ * below what the stream has consumed are ignored (pass all of them or only the new ones, ascending); the streams of one call may be at different stages; the
+ * call is ordered with the device's other batch calls.  A slot of  new + (new >> 8) + 4096 + 64 * (newFlushes + 4)  bytes always suffices, `new` being the
+ * source bytes behind what the stream has consumed.  Besides a size d_result[i] answers 201 (the total exceeds the level's window: the bundled library's
+ * stream takes over from byte 0), ZSTD_error_stage_wrong (60: the state is closed already, was begun with another level or checksum flag, or the source is
+ * shorter than what was consumed) and ZSTD_error_dstSize_tooSmall (70).  After an error the state is dead and answers that code from then on.
+ *
+ * Host form, after ZSTD_CStream (ZSTD_createCStream / ZSTD_freeCStream / ZSTD_CCtx_reset(session_only) / ZSTD_compressStream2): the handle owns the device copy
+ * of the source so far, the state and a staging slot, so only new bytes cross the link, once.  zjni_cstream_compress: `src` holds the NEW bytes only;
+ * directive 0 (ZSTD_e_continue) buffers them and returns 0, 1 (ZSTD_e_flush) and 2 (ZSTD_e_end) return the count of new frame bytes written to dst.  With
+ * dstCapacity below the bound above (new = every byte not yet flushed, these included; newFlushes = 1) the call answers dstSize_tooSmall before touching
+ * anything: neither the buffered bytes nor the state change.  201 beyond the window leaves the handle dead (the caller's CPU path replays the stream) until
+ * zjni_cstream_reset, which starts the next frame with the same parameters.  ZSTD_e_end as the first directive on a fresh handle, without bytes, is the
+ * knownEmpty case above.  A handle is bound to the device of the thread that created it and serves one thread at a time. */
+size_t zjni_cstream_state_bytes(int level);
+size_t zjni_compress_stream_continue_batch_device(const void* d_src, const uint64_t* d_src_off, void* d_dst, const uint64_t* d_dst_off,
+                                                  uint64_t* d_result, size_t n, int level, int checksum,
+                                                  const uint32_t* d_flush_at, const uint64_t* d_flush_off, const uint32_t* d_mode,
+                                                  void* d_state, void* stream);
+typedef struct zjni_cstream zjni_cstream;
+zjni_cstream* zjni_createCStream(int level, int checksum);
+size_t zjni_freeCStream(zjni_cstream* cs);
+size_t zjni_cstream_reset(zjni_cstream* cs);
+size_t zjni_cstream_compress(zjni_cstream* cs, void* dst, size_t dstCapacity, const void* src, size_t srcSize, int directive);
+
 /* ---- compression dictionaries ----
  * zjni_cdict == ZSTD_CDict as zstd-jni holds it in ZstdDictCompress.nativePtr (J/ZstdDictCompress.java;
  * N/jni_fast_zstd.c:18-66: init = ZSTD_createCDict(dict, size, level), free = ZSTD_freeCDict).  The dictionary is

@@ -202,6 +202,19 @@ def lib():
     L.zjni_compress_stream.argtypes = [vp, sz, vp, sz, C.c_int, C.c_int, vp, sz, C.c_int, C.c_int]
     L.zjni_compress_stream_batch_device.restype = sz
     L.zjni_compress_stream_batch_device.argtypes = [vp, vp, vp, vp, vp, sz, C.c_int, C.c_int, vp, vp, vp, vp]
+    if hasattr(L, "zjni_cstream_compress"):              # (absent from older variant libraries loaded through ZJNI_LIB for A/B runs)
+        L.zjni_cstream_state_bytes.restype = sz
+        L.zjni_cstream_state_bytes.argtypes = [C.c_int]
+        L.zjni_compress_stream_continue_batch_device.restype = sz
+        L.zjni_compress_stream_continue_batch_device.argtypes = [vp, vp, vp, vp, vp, sz, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+        L.zjni_createCStream.restype = vp
+        L.zjni_createCStream.argtypes = [C.c_int, C.c_int]
+        L.zjni_freeCStream.restype = sz
+        L.zjni_freeCStream.argtypes = [vp]
+        L.zjni_cstream_reset.restype = sz
+        L.zjni_cstream_reset.argtypes = [vp]
+        L.zjni_cstream_compress.restype = sz
+        L.zjni_cstream_compress.argtypes = [vp, vp, sz, vp, sz, C.c_int]
     if hasattr(L, "zjni_inspect"):                       # (absent from older variant libraries loaded through ZJNI_LIB for A/B runs, like zjni_last_decode_lists2)
         L.zjni_inspect.restype = sz
         L.zjni_inspect.argtypes = [vp, sz, vp]
@@ -230,7 +243,8 @@ EXPORTS = ("zjni_version", "zjni_device_count", "zjni_init", "zjni_shutdown", "z
            "zjni_createAggregator", "zjni_freeAggregator", "zjni_aggregator_compress", "zjni_aggregator_decompress", "zjni_aggregator_stats",
            "zjni_last_route", "zjni_route_kernel", "zjni_build_stamp", "zjni_compress_stream", "zjni_compress_stream_batch_device", "zjni_frame_extent", "zjni_last_lists", "zjni_last_decode_lists", "zjni_last_decode_lists2",
            "zjni_compress_batch_begin", "zjni_decompress_batch_begin", "zjni_batch_finish", "zjni_pack_batch_device2",
-           "zjni_inspect", "zjni_inspect_batch_device", "zjni_decompress_offsets_device", "zjni_decompress_batch_device_sized")
+           "zjni_inspect", "zjni_inspect_batch_device", "zjni_decompress_offsets_device", "zjni_decompress_batch_device_sized",
+           "zjni_cstream_state_bytes", "zjni_compress_stream_continue_batch_device", "zjni_createCStream", "zjni_freeCStream", "zjni_cstream_reset", "zjni_cstream_compress")
 
 
 # --------------------------------------------------------------------------- Java API mirror --
@@ -628,6 +642,62 @@ def compress_stream(data, level=3, checksum=False, flush_at=(), final=True, know
     if L.zjni_isError(r):
         raise ZstdException(r)
     return dst.raw[:r]
+
+
+class ZstdCompressStream:
+    """A live compress stream over zjni_cstream_* (ZSTD_CStream with ZSTD_compressStream2): write() buffers, flush() and close() return the frame's NEW
+    bytes — the stream's state stays on the device, so a flush compresses only what was written since the last one and only those bytes cross the
+    link.  The outputs, concatenated, are compress_stream()'s frame for everything written.  close() ends the frame; reset() starts the next one on
+    the same handle; free() (or the garbage collector) releases the device memory.  `capacity`: the destination's size (default: the documented bound);
+    ZstdException(70) for one below the bound leaves the stream as it was, ZstdException(201) beyond the level's window leaves it dead until reset()."""
+
+    def __init__(self, level=3, checksum=False):
+        self._ptr = lib().zjni_createCStream(level, 1 if checksum else 0)
+        if not self._ptr:
+            raise ZstdException(42 if level > 3 else ERR_NO_DEVICE, "zjni_createCStream failed")
+        self._pending = 0
+
+    def _call(self, data, directive, capacity=None):
+        if not self._ptr:
+            raise RuntimeError("Closed")
+        L = lib()
+        data = bytes(data)
+        fresh = self._pending + len(data)
+        cap = fresh + (fresh >> 8) + 4096 + 64 * 5 if capacity is None else capacity
+        dst = C.create_string_buffer(max(cap, 1))
+        r = L.zjni_cstream_compress(self._ptr, dst, cap, data, len(data), directive)
+        if L.zjni_isError(r):
+            raise ZstdException(r)
+        self._pending = fresh if directive == 0 else 0
+        return dst.raw[:r]
+
+    def write(self, data):
+        self._call(data, 0)
+
+    def flush(self, capacity=None):
+        return self._call(b"", 1, capacity)
+
+    def close(self, capacity=None):
+        return self._call(b"", 2, capacity)
+
+    def reset(self):
+        if not self._ptr:
+            raise RuntimeError("Closed")
+        r = lib().zjni_cstream_reset(self._ptr)
+        if lib().zjni_isError(r):
+            raise ZstdException(r)
+        self._pending = 0
+
+    def free(self):
+        if self._ptr:
+            lib().zjni_freeCStream(self._ptr)
+            self._ptr = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
 
 
 def decompress_batch(frames, capacities, dictionary=None):

@@ -134,6 +134,38 @@ def decompress_sized(src_blob, src_off, dst_blob=None, dictionary=None, align=1,
     return dst_blob, dst_off, results, total
 
 
+def stream_states(n, level, device="cuda"):
+    """n compress-stream states of zjni_cstream_state_bytes(level) bytes each, zeroed: streams on which nothing has been done."""
+    size = lib().zjni_cstream_state_bytes(level)
+    if not size:
+        raise ZstdException(42, "compress streams are not served at level %d" % level)
+    return torch.zeros(n * size, dtype=torch.uint8, device=device)
+
+
+def compress_stream_continue(src_blob, src_off, dst_blob, dst_off, states, level=3, checksum=False, flush_at=None, flush_off=None, mode=None, results=None):
+    """Enqueue zjni_compress_stream_continue_batch_device on the current stream: src slot i holds everything written to stream i so far, dst slot i
+    receives the frame's NEW bytes only, results[i] is their count (0: nothing flushed since the last call) or a negative error code.
+    flush_at uint32 / flush_off int64[n + 1]: the flush positions of stream i (all of them or only the new ones); mode uint32[n]: 1 = close,
+    | 2 = closed before anything else (None: all close)."""
+    n = src_off.numel() - 1
+    if results is None:
+        results = torch.empty(n, dtype=torch.int64, device=src_blob.device)
+    if states.dtype != torch.uint8 or not states.is_contiguous() or states.numel() < n * lib().zjni_cstream_state_bytes(level):
+        raise ValueError("compress_stream_continue: states must be stream_states(n, level)")
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    _check(lib().zjni_compress_stream_continue_batch_device(src_blob.data_ptr(), src_off.data_ptr(), dst_blob.data_ptr(), dst_off.data_ptr(), results.data_ptr(), n, level,
+                                                            1 if checksum else 0, ptr(flush_at), ptr(flush_off), ptr(mode), states.data_ptr(), _stream_ptr()))
+    return results
+
+
+def stream_state_info(states, level):
+    """The header words of every state (zj_encode.h ZEStreamState) as int64[n] tensors: consumed (source bytes compressed so far), produced (frame bytes
+    written so far), parsed / blocks (sums over the blocks handed to the block compressor: their sizes, their count), closed, error."""
+    size = lib().zjni_cstream_state_bytes(level)
+    words = states.view(torch.int32).view(-1, size // 4)[:, :16].to(torch.int64)
+    return {"error": words[:, 3], "closed": words[:, 4], "consumed": words[:, 5], "produced": words[:, 6], "parsed": words[:, 9], "blocks": words[:, 10]}
+
+
 def pack(results, dst_blob, dst_off, out=None, out_off=None):
     """Tightly pack a compress batch's variable-size outputs (sizes = results) into one blob:
     returns (packed_blob, packed_off int64[n+1]).  With `out` (uint8, capacity >= sum of sizes) and `out_off`

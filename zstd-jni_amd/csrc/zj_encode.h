@@ -2345,6 +2345,142 @@ ZJ_DEV u64 ze_compress_stream(const G& g, ZEncShared& sh, u8* lds, const u8* src
     return pos + tail;
 }
 
+// ---- stream frames CONTINUED from device state: ZSTD_compressStream2 with ZSTD_e_flush / ZSTD_e_end on a live ZSTD_CStream (N/compress/zstd_compress.c:6103-6300) ----
+// ze_compress_stream keeps nothing between calls: a stream flushed k times is parsed and entropy-coded from byte 0 k + 1 times.  Here the stream's state stays in
+// caller-owned device memory, so a call compresses only the bytes behind the last flush and writes only the frame's new bytes.  What a block of a frame hands to
+// the next one is little, and all of it is in ZEStreamState: the hash table(s), parsed in place; the repcodes and the Huffman table of the last block that was
+// emitted compressed (ze_compress_t's tail: blkRep, dictHufRep, dictHufMaxSV, dictCodes); whether a block has been emitted at all (RLE blocks are never the frame's
+// first); and the frame bytes produced so far (`savings` of rule (iii)).  A call ends at a flush position or at the end, where the reference's 128 KiB pieces start
+// again (rule (iv)), so no piece is ever open between calls.  Every decision depends only on the bytes before it, hence the calls' outputs, concatenated, are the
+// frame ze_compress_stream writes in one call: tests/test_emu_cstream.py, tests/test_gpu_cstream.py.
+// An all-zero state is a stream on which nothing has been done.  After an error the state is dead: it answers that code from then on.
+#define ZE_STREAM_STATE_HDR 1280u                                   /* bytes before the tables (a multiple of 256) */
+struct ZEStreamState {
+    u32 begun;                      // the first call has been seen: levelWord and checksum are its
+    u32 levelWord, checksum;
+    u32 error;                      // sticky
+    u32 closed;                     // the epilogue is written
+    u32 consumed;                   // source bytes compressed so far: a flush position, or the end
+    u32 produced;                   // frame bytes written so far, the header's included
+    u32 notFirst;                   // a block has been emitted (isFirst = !notFirst)
+    u32 lastFlag;                   // the last emitted block carried the last-block flag (else close() wrote the empty last block)
+    u32 parsedBytes, blocks;        // sums over the blocks handed to the block compressor: their sizes, their count — a stream never parsed twice ends with parsedBytes == its length
+    u32 blkRep[2];
+    u32 hufRep, hufMaxSV;           // ZEncShared::dictHufRep / dictHufMaxSV between blocks
+    u32 hufCodes[256];              // ZEncShared::dictCodes: the previous compressed block's Huffman table
+    u32 pad[(ZE_STREAM_STATE_HDR - (15u + 256u) * 4u) / 4u];
+    u32 tables[1];                  // (1 << hashLog) [+ (1 << chainLog)] entries of the level's unknown-size row
+};
+static_assert(offsetof(ZEStreamState, tables) == ZE_STREAM_STATE_HDR, "the tables start behind the header");
+ZJ_HD u32 ze_stream_table_entries(u32 levelWord) {
+    ZEParams const p = ze_params_of(levelWord, (256u << 10) + 1u);
+    return (1u << p.hashLog) + (p.strategy == 2 ? (1u << p.chainLog) : 0u);
+}
+// bytes of one stream's state, a multiple of 256; 0 for a level the streams do not serve
+ZJ_HD u32 ze_stream_state_bytes(u32 levelWord) {
+    u32 const lv = ZE_LW_LEVEL(levelWord);
+    return (lv < 1u || lv > 3u) ? 0u : ZE_STREAM_STATE_HDR + ze_stream_table_entries(levelWord) * 4u;
+}
+// dst receives the NEW frame bytes only; the return value is their count (0: nothing was flushed since the last call) or ZJ_ERR64(code): 201 beyond the window,
+// 60 (stage_wrong) for a closed state, another level word or checksum flag than the first call's, or srcSize < consumed, 70 when dst runs out.
+// Flush positions <= consumed are ignored (the caller may pass all of them or only the new ones); always new + (new >> 8) + 4096 + 64 * (new flushes + 4) bytes suffice.
+template <class G>
+ZJ_DEV u64 ze_compress_stream_resume(const G& g, ZEncShared& sh, u8* lds, const u8* src, u32 srcSize, u8* dst, u32 dstCap, u32 level, u8* ws, ZjProf& pf, u32 flags, ZEStreamState* stt, u32 ldsBytes,
+                                     const u32* flushAt, u32 nFlush, u32 final, u32 knownEmpty) {
+    u32 const lv = ZE_LW_LEVEL(level);
+    u32 const wlog = ze_stream_window_log(lv);
+    u32 const ck = (flags & ZE_FLAG_CHECKSUM) ? 1u : 0u, tail = ck ? 4u : 0u;
+    u32* const tables = stt->tables;
+    u32 code = ZJ_UNI(stt->error);
+    bool const fresh = !ZJ_UNI(stt->begun);
+    if (!code) {
+        if (lv < 1u || lv > 3u || srcSize > (1u << wlog) || srcSize > ZE_MULTI_MAX) code = 201;
+        else if (!fresh && (ZJ_UNI(stt->closed) || ZJ_UNI(stt->levelWord) != level || ZJ_UNI(stt->checksum) != ck || srcSize < ZJ_UNI(stt->consumed))) code = 60;      // ZSTD_error_stage_wrong
+    }
+    g.sync();
+    if (code) { GRP_SERIAL(g) { stt->begun = 1; stt->error = code; } zj_mem_order(); g.sync(); return ZJ_ERR64(code); }
+    u32 const paramSize = srcSize > (256u << 10) ? srcSize : (256u << 10) + 1u;
+    ZEParams const p = ze_params_of(level, paramSize);
+    if (fresh) {
+        GRP_FOR(g, i, ze_stream_table_entries(level)) tables[i] = 0;
+        GRP_SERIAL(g) {
+            stt->begun = 1; stt->levelWord = level; stt->checksum = ck; stt->closed = 0; stt->consumed = 0; stt->produced = 0; stt->notFirst = 0; stt->lastFlag = 0;
+            stt->parsedBytes = 0; stt->blocks = 0; stt->blkRep[0] = 1; stt->blkRep[1] = 4; stt->hufRep = ZC_REPEAT_NONE; stt->hufMaxSV = 0;
+        }
+        zj_mem_order();
+        g.sync();
+    }
+    u32 const consumed = ZJ_UNI(stt->consumed), produced = ZJ_UNI(stt->produced);
+    u32 total = srcSize;                                                                  // what the stream has consumed after this call: everything when closing, up to the last flush otherwise
+    if (!final) { total = consumed; for (u32 i = 0; i < nFlush; i++) if (flushAt[i] <= srcSize && flushAt[i] > total) total = flushAt[i]; }
+    if (!final && total == consumed) return 0;                                            // nothing was flushed since the last call
+    GRP_FOR(g, s, 256) sh.dictCodes[s] = stt->hufCodes[s];
+    GRP_SERIAL(g) { sh.blkRep[0] = stt->blkRep[0]; sh.blkRep[1] = stt->blkRep[1]; sh.dictHufRep = stt->hufRep; sh.dictHufMaxSV = stt->hufMaxSV; }
+    u32 pos = 0, isFirst = ZJ_UNI(stt->notFirst) ? 0u : 1u, fi = 0, parsed = 0, blocks = 0; bool lastSeen = false;
+    if (produced == 0u) {                                                                 // the header goes out with the first bytes the stream ever produces
+        if (dstCap < 18u) code = ZJ_E_DSTSIZE_TOO_SMALL;
+        else {
+            bool const emptyKnown = final && knownEmpty && srcSize == 0u;
+            GRP_SERIAL(g) {
+                st32(dst, 0xFD2FB528u);
+                if (emptyKnown) { dst[4] = (u8)(0x20u + (tail ? 4u : 0u)); dst[5] = 0; }
+                else { dst[4] = (u8)(tail ? 4u : 0u); dst[5] = (u8)((wlog - 10u) << 3); }
+            }
+            pos = 6;
+        }
+    }
+    g.sync();
+    for (u32 chunk = consumed, seg = consumed; chunk < total && !code; ) {
+        while (fi < nFlush && flushAt[fi] <= seg) fi++;                                   // (flushes of earlier calls, flushes with nothing buffered)
+        bool const haveFlush = fi < nFlush && flushAt[fi] <= total;
+        u32 const segEnd = haveFlush ? flushAt[fi] : total;
+        u32 const chunkEnd = chunk + 131072u < segEnd ? chunk + 131072u : segEnd;
+        bool const flushed = haveFlush && chunkEnd == segEnd;
+        bool const endChunk = final && chunkEnd == total && (chunkEnd - chunk) != 131072u && !flushed;
+        i64 savings = (i64)chunk - (i64)(produced + pos);                                 // consumedSrcSize - producedCSize over the whole frame
+        for (u32 at = chunk; at < chunkEnd; ) {
+            if (p.strategy == 2 && chunkEnd - at >= 131072u && savings >= 3) {
+                u32 const bs = zp_split_by_chunks_g(g, src + at, (u32*)lds);
+                GRP_SERIAL(g) { sh.tmp[0] = bs; }
+            } else GRP_SERIAL(g) { sh.tmp[0] = zp_block_size(src + at, chunkEnd - at, p.strategy, savings, (u32*)lds); }
+            g.sync();
+            u32 const blockSize = ZJ_UNI(sh.tmp[0]);
+            g.sync();
+            ZEBlockArgs ba; ba.frameBase = src; ba.frameSize = srcSize; ba.paramSize = paramSize; ba.start = at; ba.isFirst = isFirst; ba.lastBlock = (endChunk && at + blockSize == chunkEnd) ? 1u : 0u; ba.tables = tables;
+            ba.serialParse = ((flags & ZE_FLAG_MULTI_SERIAL) ? 1u : ((flags & ZE_FLAG_MULTI_NOCARRY) ? 2u : 0u)) | ((flags & ZE_FLAG_MULTI_FAST_SERIAL) ? 4u : 0u);
+            u64 const r = ze_compress_t<G, u32>(g, sh, lds, src + at, blockSize, dst + pos, dstCap - pos, level, ws, pf, nullptr, 0u, nullptr, ldsBytes, &ba);
+            parsed += blockSize; blocks++;
+            if (r > ZJ_ERR64(256)) { code = (u32)((u64)0 - r); break; }
+            lastSeen = ba.lastBlock != 0;
+            savings += (i64)blockSize - (i64)r;
+            at += blockSize; pos += (u32)r; isFirst = 0;
+        }
+        chunk = chunkEnd; if (chunkEnd == segEnd) seg = segEnd;
+    }
+    if (final && !code) {
+        if (dstCap < pos + 3u + tail) code = ZJ_E_DSTSIZE_TOO_SMALL;
+        else {
+            if (!lastSeen) { GRP_SERIAL(g) { dst[pos] = 1; dst[pos + 1] = 0; dst[pos + 2] = 0; } pos += 3; }      // ZSTD_writeEpilogue: an empty raw last block
+            if (tail) {
+                u64 const h = zj_xxh64(g, src, srcSize);
+                GRP_SERIAL(g) { st32(dst + pos, (u32)h); }
+                pos += tail;
+            }
+        }
+    }
+    g.sync();
+    if (code) { GRP_SERIAL(g) { stt->error = code; } zj_mem_order(); g.sync(); return ZJ_ERR64(code); }
+    GRP_FOR(g, s, 256) stt->hufCodes[s] = sh.dictCodes[s];
+    GRP_SERIAL(g) {
+        stt->consumed = total; stt->produced = produced + pos; stt->notFirst = isFirst ? 0u : 1u; stt->lastFlag = lastSeen ? 1u : 0u; stt->closed = final ? 1u : 0u;
+        stt->parsedBytes += parsed; stt->blocks += blocks;
+        stt->blkRep[0] = sh.blkRep[0]; stt->blkRep[1] = sh.blkRep[1]; stt->hufRep = sh.dictHufRep; stt->hufMaxSV = sh.dictHufMaxSV;
+    }
+    zj_mem_order();
+    g.sync();
+    return pos;
+}
+
 // ---- multi-block frames, PIPELINED (round 6): a parse wave one block ahead of an entropy wave ------------------------------------------------------------
 // ze_compress_multi is a chain per frame — size of the next block, parse, entropy stage, block by block on one wave: 8 x (16 + 11) ms for a 1 MiB frame, and a
 // batch of a thousand such frames (BASELINE config 1) leaves three quarters of the device idle while every frame waits for its own chain.  What block b + 1's

@@ -1003,6 +1003,33 @@ __global__ __launch_bounds__(64, ZJ_MULTI_WAVES) void zj_encode_stream_kernel(co
     }
 }
 
+// Stream frames continued from their state (ze_compress_stream_resume, zj_encode.h): the loop above with stream i's ZEStreamState at state + i * stateStride — its
+// tables are parsed in place, so the launch takes no table slots, only the scratch slots.  A kernel of its own so that the one above keeps its registers.
+__global__ __launch_bounds__(64, ZJ_MULTI_WAVES) void zj_encode_stream_continue_kernel(const u8* __restrict__ src, const u64* __restrict__ srcOff, u8* __restrict__ dst, const u64* __restrict__ dstOff,
+                                                               u64* __restrict__ result, u32 level, u32 count, u32* workCounter, u8* scratch, u8* state, u64 stateStride, u32 flags, u32 ldsBytes,
+                                                               const u32* __restrict__ flushAt, const u64* __restrict__ flushOff, const u32* __restrict__ mode) {
+    __shared__ ZEncShared sh;
+    ZjProf pf; pf.start(nullptr);
+    Grp<64> g;
+    if (threadIdx.x == 0) { sh.dictLoaded = 0; sh.ctDict[0] = 0; sh.ctDict[1] = 0; sh.ctDict[2] = 0; }
+    __syncthreads();
+    u8* const ws = scratch + (size_t)blockIdx.x * ZE_SCRATCH_BYTES;
+    for (;;) {
+        u32 const i = zj_next_index(workCounter);
+        if (i >= count) break;
+        u64 const s0 = zj_uni64(srcOff[i]), s1 = zj_uni64(srcOff[i + 1]), d0 = zj_uni64(dstOff[i]), d1 = zj_uni64(dstOff[i + 1]);
+        u64 const cap = d1 - d0, size64 = s1 - s0;
+        u32 const capU = (u32)(cap > 0xFFFFFFFFull ? 0xFFFFFFFFull : cap);
+        u32 const size = size64 > ZE_MULTI_MAX ? ZE_MULTI_MAX + 1u : (u32)size64;              // (beyond every window: 201, and the state is dead)
+        u64 const f0 = flushOff ? zj_uni64(flushOff[i]) : 0, f1 = flushOff ? zj_uni64(flushOff[i + 1]) : 0;
+        u32 const md = mode ? ZJ_UNI(mode[i]) : 1u;
+        u64 const r = ze_compress_stream_resume(g, sh, zj_dyn_lds, src + s0, size, dst + d0, capU, level, ws, pf, flags, (ZEStreamState*)(state + (size_t)i * stateStride), ldsBytes,
+                                                flushAt + f0, (u32)(f1 - f0), md & 1u, (md >> 1) & 1u);
+        if (threadIdx.x == 0) result[i] = r;
+        __syncthreads();
+    }
+}
+
 // ZSTD_createCDict on the device: one workgroup digests the dictionary held in `out` (header, zeroed tables, raw bytes)
 __global__ __launch_bounds__(64) void zj_cdict_digest_kernel(u32 dictSize, u32 level, ZECDictDev* out) {
     __shared__ ZDecShared sh;
@@ -1218,6 +1245,7 @@ struct DevState {
     std::atomic<unsigned>* slotTicket = nullptr;
     std::mutex* hostDecompMu = nullptr;
     u32* multiTables = nullptr; int multiGrid = 0;    // multi-block frames: frame-wide hash tables, one set per resident workgroup
+    int contGrid = 0;                                 // resident workgroups of zj_encode_stream_continue_kernel (0: not asked yet)
     u32 lastPipeMax = 0;                              // what the last compress call passed to zj_pipe_route (diagnostics: zjni_last_lists)
     int pipeGrid = 0;                                 // ... and the resident workgroups of the pipelined kernel (two waves, two scratch slots each); 0: not available
     u8* cdBuf = nullptr; size_t cdBufCap = 0; size_t cdSliceCap = 0;
@@ -2606,6 +2634,113 @@ size_t zjni_compress_stream(void* dst, size_t dstCap, const void* src, size_t sr
     if (out > cap) return ZJNI_ERR(70);
     if (hipMemcpyAsync(sl->hPinned + oDst, sl->dStage + oDst, out, hipMemcpyDeviceToHost, hst) != hipSuccess || hipStreamSynchronize(hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
     memcpy(dst, sl->hPinned + oDst, out);
+    return out;
+}
+// ---- stream frames continued from device state (include/zjni_amd.h; ze_compress_stream_resume) ----
+size_t zjni_cstream_state_bytes(int level) {
+    if (level == 0) level = 3;
+    return level > 3 ? 0 : (size_t)ze_stream_state_bytes((u32)zj_negative_word(level));
+}
+size_t zjni_compress_stream_continue_batch_device(const void* d_src, const uint64_t* d_src_off, void* d_dst, const uint64_t* d_dst_off, uint64_t* d_result, size_t n, int level, int checksum,
+                                                  const uint32_t* d_flush_at, const uint64_t* d_flush_off, const uint32_t* d_mode, void* d_state, void* stream) {
+    if (level == 0) level = 3;
+    if (level > 3) return ZJNI_ERR(42);
+    level = zj_negative_word(level);
+    DevState* d = cur_state();
+    if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (n == 0) return 0;
+    if (n > 0xFFFFFFFFull || !d_state) return ZJNI_ERR(72);
+    BatchOrder order(d, stream);
+    hipStream_t st = (hipStream_t)stream;
+    if (!d->contGrid) {                                               // resident workgroups: as zj_encode_stream_kernel's, a scratch slot each
+        int perCU = 8, fit = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&fit, zj_encode_stream_continue_kernel, 64, sizeof(ZEEntropy)) == hipSuccess && fit >= 1 && fit < perCU) perCU = fit;
+        d->contGrid = d->numCU * perCU; if (d->contGrid > d->encGrid) d->contGrid = d->encGrid;
+    }
+    u32* const ctr = d->counters + 226;
+    if (hipMemsetAsync(ctr, 0, 4, st) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    u32 const gc = (u32)(n < (size_t)d->contGrid ? n : (size_t)d->contGrid);
+    u32 flags = checksum ? ZE_FLAG_CHECKSUM : 0u;                     // the block parses: zjni_compress_stream_batch_device's choices
+    if (const char* ov = zj_tune("ZJNI_MULTI_WAVE")) { int const v = atoi(ov); flags |= v == 0 ? ZE_FLAG_MULTI_SERIAL : (v == 2 ? ZE_FLAG_MULTI_NOCARRY : 0u); }
+    {   const char* const ov = zj_tune("ZJNI_MULTI_WAVE_FAST"); if (!(ov && atoi(ov) == 1)) flags |= ZE_FLAG_MULTI_FAST_SERIAL; }
+    hipLaunchKernelGGL(zj_encode_stream_continue_kernel, dim3(gc), dim3(64), (u32)sizeof(ZEEntropy), st, (const u8*)d_src, (const u64*)d_src_off, (u8*)d_dst, (const u64*)d_dst_off,
+                       (u64*)d_result, (u32)level, (u32)n, ctr, d->encScratch, (u8*)d_state, (u64)ze_stream_state_bytes((u32)level), flags, (u32)sizeof(ZEEntropy),
+                       (const u32*)d_flush_at, (const u64*)d_flush_off, (const u32*)d_mode);
+    return hipGetLastError() == hipSuccess ? 0 : ZJNI_ERR(ZJNI_ERROR_no_device);
+}
+// The host form: one stream's handle.  Device: [meta 256][state][source so far, up to the window][new frame bytes]; pinned: [meta 256][bytes not yet flushed][new frame bytes].
+// meta: [srcOff 2][dstOff 2][result 1][flushOff 2][mode, pad][flush position, pad] (u64 words 0-8).
+struct zjni_cstream {
+    int ordinal, level, checksum;
+    size_t window, outCap, stateBytes;
+    u8* dBuf; u8* hPinned; hipStream_t st;
+    size_t flushed, pending;                   // source bytes on the device (all of them flushed), bytes buffered in hPinned behind them
+    bool touched, closed; size_t dead;         // dead: the code every call answers until the handle is reset
+};
+static inline size_t zj_cstream_bound(size_t fresh, size_t flushes) { return fresh + (fresh >> 8) + 4096 + 64 * (flushes + 4); }
+zjni_cstream* zjni_createCStream(int level, int checksum) {
+    DevState* d = cur_state();
+    if (level == 0) level = 3;
+    if (!d || level > 3) return nullptr;
+    zjni_cstream* cs = new zjni_cstream();
+    cs->ordinal = d->ordinal; cs->level = level; cs->checksum = checksum ? 1 : 0;
+    cs->window = (size_t)1 << ze_stream_window_log(level < 0 ? 1u : (u32)level);
+    cs->outCap = zj_cstream_bound(cs->window, 1); cs->stateBytes = zjni_cstream_state_bytes(level);
+    cs->dBuf = nullptr; cs->hPinned = nullptr; cs->st = nullptr;
+    if (hipMalloc(&cs->dBuf, 256 + cs->stateBytes + cs->window + cs->outCap) != hipSuccess || hipHostMalloc(&cs->hPinned, 256 + cs->window + cs->outCap, hipHostMallocDefault) != hipSuccess
+        || hipStreamCreateWithFlags(&cs->st, hipStreamNonBlocking) != hipSuccess || zjni_isError(zjni_cstream_reset(cs))) { (void)hipGetLastError(); (void)zjni_freeCStream(cs); return nullptr; }
+    return cs;
+}
+size_t zjni_freeCStream(zjni_cstream* cs) {
+    if (!cs) return 0;
+    (void)hipSetDevice(cs->ordinal);
+    if (cs->st) { (void)hipStreamSynchronize(cs->st); (void)hipStreamDestroy(cs->st); }
+    if (cs->dBuf) (void)hipFree(cs->dBuf);
+    if (cs->hPinned) (void)hipHostFree(cs->hPinned);
+    if (t_dev >= 0) (void)hipSetDevice(t_dev);
+    delete cs;
+    return 0;
+}
+size_t zjni_cstream_reset(zjni_cstream* cs) {
+    if (!cs) return ZJNI_ERR(72);
+    if (cs->ordinal != t_dev && t_dev >= 0) return ZJNI_ERR(32);
+    cs->flushed = 0; cs->pending = 0; cs->touched = false; cs->closed = false; cs->dead = 0;
+    if (hipMemsetAsync(cs->dBuf + 256, 0, cs->stateBytes, cs->st) != hipSuccess || hipStreamSynchronize(cs->st) != hipSuccess) return cs->dead = ZJNI_ERR(ZJNI_ERROR_no_device);
+    return 0;
+}
+size_t zjni_cstream_compress(zjni_cstream* cs, void* dst, size_t dstCap, const void* src, size_t srcSize, int directive) {
+    if (!cs || (srcSize && !src) || (dstCap && !dst)) return ZJNI_ERR(72);
+    if (directive < 0 || directive > 2) return ZJNI_ERR(42);
+    if (cs->ordinal != t_dev && t_dev >= 0) return ZJNI_ERR(32);                          // made on another device
+    if (cs->dead) return cs->dead;
+    if (cs->closed) return cs->dead = ZJNI_ERR(60);
+    if (srcSize > cs->window || cs->flushed + cs->pending + srcSize > cs->window) return cs->dead = ZJNI_ERR(201);      // beyond the window: the caller's CPU path replays the stream
+    if (directive != 0 && dstCap < zj_cstream_bound(cs->pending + srcSize, 1)) return ZJNI_ERR(70);                     // (nothing was touched: the call may be made again with more room)
+    bool const knownEmpty = directive == 2 && !cs->touched && srcSize == 0;
+    cs->touched = true;
+    if (srcSize) memcpy(cs->hPinned + 256 + cs->pending, src, srcSize);
+    cs->pending += srcSize;
+    if (directive == 0) return 0;                                                           // buffered until a flush
+    size_t const total = cs->flushed + cs->pending;
+    size_t const oState = 256, oSrc = oState + cs->stateBytes, oDst = oSrc + cs->window;
+    u64* const h = (u64*)cs->hPinned;
+    h[0] = 0; h[1] = total; h[2] = 0; h[3] = cs->outCap; h[4] = 0; h[5] = 0; h[6] = directive == 1 ? 1 : 0;
+    ((u32*)(h + 7))[0] = (directive == 2 ? 1u : 0u) | (knownEmpty ? 2u : 0u); ((u32*)(h + 7))[1] = 0; ((u32*)(h + 8))[0] = (u32)total; ((u32*)(h + 8))[1] = 0;
+    u8* const dv = cs->dBuf;
+    auto fail = [&](size_t code) { (void)hipStreamSynchronize(cs->st); return cs->dead = code; };
+    if (hipMemcpyAsync(dv, h, 72, hipMemcpyHostToDevice, cs->st) != hipSuccess) return fail(ZJNI_ERR(ZJNI_ERROR_no_device));
+    if (cs->pending && hipMemcpyAsync(dv + oSrc + cs->flushed, cs->hPinned + 256, cs->pending, hipMemcpyHostToDevice, cs->st) != hipSuccess) return fail(ZJNI_ERR(ZJNI_ERROR_no_device));
+    size_t const r = zjni_compress_stream_continue_batch_device(dv + oSrc, (const u64*)dv, dv + oDst, (const u64*)(dv + 16), (u64*)(dv + 32), 1, cs->level, cs->checksum,
+                                                                (const u32*)(dv + 64), (const u64*)(dv + 40), (const u32*)(dv + 56), dv + oState, cs->st);
+    if (zjni_isError(r)) return fail(r);
+    if (hipMemcpyAsync(h + 4, dv + 32, 8, hipMemcpyDeviceToHost, cs->st) != hipSuccess || hipStreamSynchronize(cs->st) != hipSuccess) return fail(ZJNI_ERR(ZJNI_ERROR_no_device));
+    size_t const out = (size_t)h[4];
+    if (zjni_isError(out)) return cs->dead = out;
+    if (out > dstCap || out > cs->outCap) return cs->dead = ZJNI_ERR(70);
+    u8* const hOut = cs->hPinned + 256 + cs->window;
+    if (out && (hipMemcpyAsync(hOut, dv + oDst, out, hipMemcpyDeviceToHost, cs->st) != hipSuccess || hipStreamSynchronize(cs->st) != hipSuccess)) return fail(ZJNI_ERR(ZJNI_ERROR_no_device));
+    if (out) memcpy(dst, hOut, out);
+    cs->flushed = total; cs->pending = 0; cs->closed = directive == 2;
     return out;
 }
 // ZstdCompressCtx.setHashLog / setChainLog (ZSTD_c_hashLog / ZSTD_c_chainLog; 0 = the library's choice) on top of level + checksum.
