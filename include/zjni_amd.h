@@ -227,7 +227,22 @@ size_t zjni_compress_stream_batch_device(const void* d_src, const uint64_t* d_sr
  * dstCapacity below the bound above (new = every byte not yet flushed, these included; newFlushes = 1) the call answers dstSize_tooSmall before touching
  * anything: neither the buffered bytes nor the state change.  201 beyond the window leaves the handle dead (the caller's CPU path replays the stream) until
  * zjni_cstream_reset, which starts the next frame with the same parameters.  ZSTD_e_end as the first directive on a fresh handle, without bytes, is the
- * knownEmpty case above.  A handle is bound to the device of the thread that created it and serves one thread at a time. */
+ * knownEmpty case above.  A handle is bound to the device of the thread that created it and serves one thread at a time.
+ *
+ * Full pieces compressed as they are written (ZSTD_e_continue as ZSTD_compressStream_generic's zcss_load stage serves it: the stream's 128 KiB input buffer is
+ * compressed the moment it is full).  Device form: bit 2 (value 4) of d_mode[i], beside 1 (close) and 2 (closed before anything else).  With it a call that
+ * does not close consumes, behind the newest flush position F it was given (F = what the stream has consumed when there is none), every full piece as well:
+ * F + ((size - F) / 131072) * 131072 bytes in all.  d_result[i] is 0 when that completes no piece.  The bit means nothing on a closing call; the streams of one
+ * call may mix all directives; the refusals, the state's layout and size are as above.  The slot bound above holds unchanged: such a call writes a prefix of
+ * what a closing call on the same bytes would write.  A piece that is full is never the frame's last block: the close behind it writes the buffered rest, or
+ * the 3-byte empty last block, which is ZstdOutputStream's frame (it closes without bytes).
+ * Host form: zjni_createCStream2(level, checksum, ZJNI_CSTREAM_EAGER); zjni_createCStream(l, c) is zjni_createCStream2(l, c, 0).  On an eager handle directive 0
+ * copies the new bytes, sends the pieces they complete to the device and launches their compression on the handle's stream WITHOUT waiting, then returns the
+ * frame bytes of the pieces launched by EARLIER calls (it waits for those), as many as dstCapacity allows; the rest stays held.  zjni_cstream_pending: the
+ * frame bytes finished or in flight and not yet handed out (it waits for the work in flight to know them; 0 on a plain handle).  Directives 1 and 2 hand out
+ * what is held first, then their own bytes, and want dstCapacity >= zjni_cstream_pending + the bound above for the bytes no piece has taken; below that they
+ * answer dstSize_tooSmall and nothing changes.  zjni_cstream_reset and zjni_freeCStream wait for the work in flight and drop it; 201 drops what is held (the
+ * CPU path replays from byte 0).  A piece in flight holds the device's batch order: other batch calls on the device run behind it. */
 size_t zjni_cstream_state_bytes(int level);
 size_t zjni_compress_stream_continue_batch_device(const void* d_src, const uint64_t* d_src_off, void* d_dst, const uint64_t* d_dst_off,
                                                   uint64_t* d_result, size_t n, int level, int checksum,
@@ -235,6 +250,9 @@ size_t zjni_compress_stream_continue_batch_device(const void* d_src, const uint6
                                                   void* d_state, void* stream);
 typedef struct zjni_cstream zjni_cstream;
 zjni_cstream* zjni_createCStream(int level, int checksum);
+#define ZJNI_CSTREAM_EAGER 1
+zjni_cstream* zjni_createCStream2(int level, int checksum, int flags);
+size_t zjni_cstream_pending(const zjni_cstream* cs);
 size_t zjni_freeCStream(zjni_cstream* cs);
 size_t zjni_cstream_reset(zjni_cstream* cs);
 size_t zjni_cstream_compress(zjni_cstream* cs, void* dst, size_t dstCapacity, const void* src, size_t srcSize, int directive);

@@ -215,6 +215,11 @@ def lib():
         L.zjni_cstream_reset.argtypes = [vp]
         L.zjni_cstream_compress.restype = sz
         L.zjni_cstream_compress.argtypes = [vp, vp, sz, vp, sz, C.c_int]
+    if hasattr(L, "zjni_createCStream2"):
+        L.zjni_createCStream2.restype = vp
+        L.zjni_createCStream2.argtypes = [C.c_int, C.c_int, C.c_int]
+        L.zjni_cstream_pending.restype = sz
+        L.zjni_cstream_pending.argtypes = [vp]
     if hasattr(L, "zjni_inspect"):                       # (absent from older variant libraries loaded through ZJNI_LIB for A/B runs, like zjni_last_decode_lists2)
         L.zjni_inspect.restype = sz
         L.zjni_inspect.argtypes = [vp, sz, vp]
@@ -244,7 +249,8 @@ EXPORTS = ("zjni_version", "zjni_device_count", "zjni_init", "zjni_shutdown", "z
            "zjni_last_route", "zjni_route_kernel", "zjni_build_stamp", "zjni_compress_stream", "zjni_compress_stream_batch_device", "zjni_frame_extent", "zjni_last_lists", "zjni_last_decode_lists", "zjni_last_decode_lists2",
            "zjni_compress_batch_begin", "zjni_decompress_batch_begin", "zjni_batch_finish", "zjni_pack_batch_device2",
            "zjni_inspect", "zjni_inspect_batch_device", "zjni_decompress_offsets_device", "zjni_decompress_batch_device_sized",
-           "zjni_cstream_state_bytes", "zjni_compress_stream_continue_batch_device", "zjni_createCStream", "zjni_freeCStream", "zjni_cstream_reset", "zjni_cstream_compress")
+           "zjni_cstream_state_bytes", "zjni_compress_stream_continue_batch_device", "zjni_createCStream", "zjni_freeCStream", "zjni_cstream_reset", "zjni_cstream_compress",
+           "zjni_createCStream2", "zjni_cstream_pending")
 
 
 # --------------------------------------------------------------------------- Java API mirror --
@@ -649,13 +655,22 @@ class ZstdCompressStream:
     bytes — the stream's state stays on the device, so a flush compresses only what was written since the last one and only those bytes cross the
     link.  The outputs, concatenated, are compress_stream()'s frame for everything written.  close() ends the frame; reset() starts the next one on
     the same handle; free() (or the garbage collector) releases the device memory.  `capacity`: the destination's size (default: the documented bound);
-    ZstdException(70) for one below the bound leaves the stream as it was, ZstdException(201) beyond the level's window leaves it dead until reset()."""
+    ZstdException(70) for one below the bound leaves the stream as it was, ZstdException(201) beyond the level's window leaves it dead until reset().
+    eager=True (zjni_createCStream2 with ZJNI_CSTREAM_EAGER): a write() that completes 128 KiB pieces launches their compression and does not wait for
+    it; write() then returns bytes, those of the pieces that earlier writes launched (`capacity`: how many at most, default all of them), and flush() /
+    close() return what is still held in front of their own bytes.  pending(): the frame bytes finished or in flight that no call has returned yet."""
 
-    def __init__(self, level=3, checksum=False):
-        self._ptr = lib().zjni_createCStream(level, 1 if checksum else 0)
+    def __init__(self, level=3, checksum=False, eager=False):
+        self._eager = bool(eager)
+        self._ptr = lib().zjni_createCStream2(level, 1 if checksum else 0, 1) if eager else lib().zjni_createCStream(level, 1 if checksum else 0)
         if not self._ptr:
             raise ZstdException(42 if level > 3 else ERR_NO_DEVICE, "zjni_createCStream failed")
         self._pending = 0
+
+    def pending(self):
+        if not self._ptr:
+            raise RuntimeError("Closed")
+        return lib().zjni_cstream_pending(self._ptr) if self._eager else 0
 
     def _call(self, data, directive, capacity=None):
         if not self._ptr:
@@ -663,16 +678,22 @@ class ZstdCompressStream:
         L = lib()
         data = bytes(data)
         fresh = self._pending + len(data)
-        cap = fresh + (fresh >> 8) + 4096 + 64 * 5 if capacity is None else capacity
+        if capacity is not None:
+            cap = capacity
+        elif directive == 0:
+            cap = self.pending()
+        else:
+            cap = self.pending() + fresh + (fresh >> 8) + 4096 + 64 * 5
         dst = C.create_string_buffer(max(cap, 1))
         r = L.zjni_cstream_compress(self._ptr, dst, cap, data, len(data), directive)
         if L.zjni_isError(r):
             raise ZstdException(r)
-        self._pending = fresh if directive == 0 else 0
+        self._pending = 0 if directive else (fresh & 131071 if self._eager else fresh)      # (an eager handle's full pieces are on their way)
         return dst.raw[:r]
 
-    def write(self, data):
-        self._call(data, 0)
+    def write(self, data, capacity=None):
+        out = self._call(data, 0, capacity)
+        return out if self._eager else None
 
     def flush(self, capacity=None):
         return self._call(b"", 1, capacity)

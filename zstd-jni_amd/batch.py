@@ -146,7 +146,8 @@ def compress_stream_continue(src_blob, src_off, dst_blob, dst_off, states, level
     """Enqueue zjni_compress_stream_continue_batch_device on the current stream: src slot i holds everything written to stream i so far, dst slot i
     receives the frame's NEW bytes only, results[i] is their count (0: nothing flushed since the last call) or a negative error code.
     flush_at uint32 / flush_off int64[n + 1]: the flush positions of stream i (all of them or only the new ones); mode uint32[n]: 1 = close,
-    | 2 = closed before anything else (None: all close)."""
+    | 2 = closed before anything else, | 4 = continue: a call that does not close also compresses every full 128 KiB piece behind the newest
+    flush (None: all close)."""
     n = src_off.numel() - 1
     if results is None:
         results = torch.empty(n, dtype=torch.int64, device=src_blob.device)

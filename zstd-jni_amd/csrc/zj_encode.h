@@ -2353,6 +2353,10 @@ ZJ_DEV u64 ze_compress_stream(const G& g, ZEncShared& sh, u8* lds, const u8* src
 // first); and the frame bytes produced so far (`savings` of rule (iii)).  A call ends at a flush position or at the end, where the reference's 128 KiB pieces start
 // again (rule (iv)), so no piece is ever open between calls.  Every decision depends only on the bytes before it, hence the calls' outputs, concatenated, are the
 // frame ze_compress_stream writes in one call: tests/test_emu_cstream.py, tests/test_gpu_cstream.py.
+// `pieces` is ZSTD_e_continue (ZSTD_compressStream_generic's zcss_load stage compresses the input buffer the moment its 128 KiB are full): a call that does not
+// close also consumes every full piece behind the newest flush.  `consumed` then stands a multiple of 128 KiB behind the last flush, which is a piece boundary
+// and therefore a block boundary, so the loop below needs no other rule; a full piece is never the last block, a later close writes the buffered rest or the
+// empty raw last block: tests/test_emu_cstream_pieces.py, tests/test_gpu_cstream_pieces.py.
 // An all-zero state is a stream on which nothing has been done.  After an error the state is dead: it answers that code from then on.
 #define ZE_STREAM_STATE_HDR 1280u                                   /* bytes before the tables (a multiple of 256) */
 struct ZEStreamState {
@@ -2386,7 +2390,7 @@ ZJ_HD u32 ze_stream_state_bytes(u32 levelWord) {
 // Flush positions <= consumed are ignored (the caller may pass all of them or only the new ones); always new + (new >> 8) + 4096 + 64 * (new flushes + 4) bytes suffice.
 template <class G>
 ZJ_DEV u64 ze_compress_stream_resume(const G& g, ZEncShared& sh, u8* lds, const u8* src, u32 srcSize, u8* dst, u32 dstCap, u32 level, u8* ws, ZjProf& pf, u32 flags, ZEStreamState* stt, u32 ldsBytes,
-                                     const u32* flushAt, u32 nFlush, u32 final, u32 knownEmpty) {
+                                     const u32* flushAt, u32 nFlush, u32 final, u32 knownEmpty, u32 pieces = 0u) {
     u32 const lv = ZE_LW_LEVEL(level);
     u32 const wlog = ze_stream_window_log(lv);
     u32 const ck = (flags & ZE_FLAG_CHECKSUM) ? 1u : 0u, tail = ck ? 4u : 0u;
@@ -2412,7 +2416,10 @@ ZJ_DEV u64 ze_compress_stream_resume(const G& g, ZEncShared& sh, u8* lds, const 
     }
     u32 const consumed = ZJ_UNI(stt->consumed), produced = ZJ_UNI(stt->produced);
     u32 total = srcSize;                                                                  // what the stream has consumed after this call: everything when closing, up to the last flush otherwise
-    if (!final) { total = consumed; for (u32 i = 0; i < nFlush; i++) if (flushAt[i] <= srcSize && flushAt[i] > total) total = flushAt[i]; }
+    if (!final) {
+        total = consumed; for (u32 i = 0; i < nFlush; i++) if (flushAt[i] <= srcSize && flushAt[i] > total) total = flushAt[i];
+        if (pieces) total += (srcSize - total) & ~131071u;                                // ZSTD_e_continue: every piece that is full behind the newest flush goes out now, as in zcss_load
+    }
     if (!final && total == consumed) return 0;                                            // nothing was flushed since the last call
     GRP_FOR(g, s, 256) sh.dictCodes[s] = stt->hufCodes[s];
     GRP_SERIAL(g) { sh.blkRep[0] = stt->blkRep[0]; sh.blkRep[1] = stt->blkRep[1]; sh.dictHufRep = stt->hufRep; sh.dictHufMaxSV = stt->hufMaxSV; }

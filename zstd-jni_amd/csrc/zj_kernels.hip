@@ -1024,7 +1024,7 @@ __global__ __launch_bounds__(64, ZJ_MULTI_WAVES) void zj_encode_stream_continue_
         u64 const f0 = flushOff ? zj_uni64(flushOff[i]) : 0, f1 = flushOff ? zj_uni64(flushOff[i + 1]) : 0;
         u32 const md = mode ? ZJ_UNI(mode[i]) : 1u;
         u64 const r = ze_compress_stream_resume(g, sh, zj_dyn_lds, src + s0, size, dst + d0, capU, level, ws, pf, flags, (ZEStreamState*)(state + (size_t)i * stateStride), ldsBytes,
-                                                flushAt + f0, (u32)(f1 - f0), md & 1u, (md >> 1) & 1u);
+                                                flushAt + f0, (u32)(f1 - f0), md & 1u, (md >> 1) & 1u, (md >> 2) & 1u);
         if (threadIdx.x == 0) result[i] = r;
         __syncthreads();
     }
@@ -2668,33 +2668,45 @@ size_t zjni_compress_stream_continue_batch_device(const void* d_src, const uint6
                        (const u32*)d_flush_at, (const u64*)d_flush_off, (const u32*)d_mode);
     return hipGetLastError() == hipSuccess ? 0 : ZJNI_ERR(ZJNI_ERROR_no_device);
 }
-// The host form: one stream's handle.  Device: [meta 256][state][source so far, up to the window][new frame bytes]; pinned: [meta 256][bytes not yet flushed][new frame bytes].
-// meta: [srcOff 2][dstOff 2][result 1][flushOff 2][mode, pad][flush position, pad] (u64 words 0-8).
+// The host form: one stream's handle.  Device: [meta slots][state][source so far, up to the window][new frame bytes]; pinned: [meta slots][source so far][new frame bytes].
+// A meta slot serves one launch: [srcOff 2][dstOff 2][result 1][flushOff 2][mode, pad][flush position, pad] (u64 words 0-8 of its 128 bytes).
+// A plain handle waits for every launch in the call that makes it and uses slot 0 only.  An eager handle (ZJNI_CSTREAM_EAGER) launches the full 128 KiB pieces from
+// ZSTD_e_continue calls without waiting: launch k of a span between two waits has slot k and its own part of the frame-byte area, which comes back to the pinned
+// area behind the kernel, so a later call finds its bytes there once the handle's stream is idle.
+#define ZJ_CS_SLOTS 32u                        /* more than a window holds pieces (16 at level 3), and every launch consumes at least one */
+#define ZJ_CS_SLOT_BYTES 128u
+#define ZJ_CS_META (ZJ_CS_SLOTS * ZJ_CS_SLOT_BYTES)
 struct zjni_cstream {
-    int ordinal, level, checksum;
+    int ordinal, level, checksum, eager;
     size_t window, outCap, stateBytes;
     u8* dBuf; u8* hPinned; hipStream_t st;
-    size_t flushed, pending;                   // source bytes on the device (all of them flushed), bytes buffered in hPinned behind them
+    size_t flushed, pending;                   // source bytes on the device (the state has consumed them, or a launch in flight will), bytes buffered in hPinned behind them
     bool touched, closed; size_t dead;         // dead: the code every call answers until the handle is reset
+    // eager: the launches whose frame bytes are not handed out yet, oldest first; part k has slot k
+    struct Part { size_t off, cap, size, given; } parts[ZJ_CS_SLOTS];
+    u32 nParts, firstPart, inFlight;           // inFlight: the newest parts, whose sizes have not been read yet
+    size_t outCursor;                          // the frame-byte area behind the newest part
 };
 static inline size_t zj_cstream_bound(size_t fresh, size_t flushes) { return fresh + (fresh >> 8) + 4096 + 64 * (flushes + 4); }
-zjni_cstream* zjni_createCStream(int level, int checksum) {
+zjni_cstream* zjni_createCStream2(int level, int checksum, int flags) {
     DevState* d = cur_state();
     if (level == 0) level = 3;
-    if (!d || level > 3) return nullptr;
+    if (!d || level > 3 || (flags & ~ZJNI_CSTREAM_EAGER)) return nullptr;
     zjni_cstream* cs = new zjni_cstream();
-    cs->ordinal = d->ordinal; cs->level = level; cs->checksum = checksum ? 1 : 0;
+    cs->ordinal = d->ordinal; cs->level = level; cs->checksum = checksum ? 1 : 0; cs->eager = (flags & ZJNI_CSTREAM_EAGER) ? 1 : 0;
     cs->window = (size_t)1 << ze_stream_window_log(level < 0 ? 1u : (u32)level);
-    cs->outCap = zj_cstream_bound(cs->window, 1); cs->stateBytes = zjni_cstream_state_bytes(level);
+    cs->outCap = zj_cstream_bound(cs->window, 1) + (cs->eager ? ZJ_CS_SLOTS * zj_cstream_bound(0, 1) : 0);      // (every launch's part is a bound of its own)
+    cs->stateBytes = zjni_cstream_state_bytes(level);
     cs->dBuf = nullptr; cs->hPinned = nullptr; cs->st = nullptr;
-    if (hipMalloc(&cs->dBuf, 256 + cs->stateBytes + cs->window + cs->outCap) != hipSuccess || hipHostMalloc(&cs->hPinned, 256 + cs->window + cs->outCap, hipHostMallocDefault) != hipSuccess
+    if (hipMalloc(&cs->dBuf, ZJ_CS_META + cs->stateBytes + cs->window + cs->outCap) != hipSuccess || hipHostMalloc(&cs->hPinned, ZJ_CS_META + cs->window + cs->outCap, hipHostMallocDefault) != hipSuccess
         || hipStreamCreateWithFlags(&cs->st, hipStreamNonBlocking) != hipSuccess || zjni_isError(zjni_cstream_reset(cs))) { (void)hipGetLastError(); (void)zjni_freeCStream(cs); return nullptr; }
     return cs;
 }
+zjni_cstream* zjni_createCStream(int level, int checksum) { return zjni_createCStream2(level, checksum, 0); }
 size_t zjni_freeCStream(zjni_cstream* cs) {
     if (!cs) return 0;
     (void)hipSetDevice(cs->ordinal);
-    if (cs->st) { (void)hipStreamSynchronize(cs->st); (void)hipStreamDestroy(cs->st); }
+    if (cs->st) { (void)hipStreamSynchronize(cs->st); (void)hipStreamDestroy(cs->st); }       // (waits for the pieces in flight)
     if (cs->dBuf) (void)hipFree(cs->dBuf);
     if (cs->hPinned) (void)hipHostFree(cs->hPinned);
     if (t_dev >= 0) (void)hipSetDevice(t_dev);
@@ -2705,8 +2717,73 @@ size_t zjni_cstream_reset(zjni_cstream* cs) {
     if (!cs) return ZJNI_ERR(72);
     if (cs->ordinal != t_dev && t_dev >= 0) return ZJNI_ERR(32);
     cs->flushed = 0; cs->pending = 0; cs->touched = false; cs->closed = false; cs->dead = 0;
-    if (hipMemsetAsync(cs->dBuf + 256, 0, cs->stateBytes, cs->st) != hipSuccess || hipStreamSynchronize(cs->st) != hipSuccess) return cs->dead = ZJNI_ERR(ZJNI_ERROR_no_device);
+    cs->nParts = 0; cs->firstPart = 0; cs->inFlight = 0; cs->outCursor = 0;                 // (the memset below runs behind the pieces in flight; their bytes are dropped)
+    if (hipMemsetAsync(cs->dBuf + ZJ_CS_META, 0, cs->stateBytes, cs->st) != hipSuccess || hipStreamSynchronize(cs->st) != hipSuccess) return cs->dead = ZJNI_ERR(ZJNI_ERROR_no_device);
     return 0;
+}
+// the handle is dead from here on: nothing stays in flight, nothing stays held
+static size_t zj_cstream_kill(zjni_cstream* cs, size_t code) {
+    (void)hipStreamSynchronize(cs->st);
+    cs->nParts = 0; cs->firstPart = 0; cs->inFlight = 0; cs->outCursor = 0;
+    return cs->dead = code;
+}
+// Enqueue one call of the device form on the handle's stream and do not wait: the `fresh` bytes behind cs->flushed go up, meta slot `slot` describes the call, the new
+// frame bytes go to [outOff, outOff + outCap) of the frame-byte area and the result to the slot's word 4 on the device.  0 or an error code.
+static size_t zj_cstream_launch(zjni_cstream* cs, u32 slot, size_t fresh, u32 mode, bool flushHere, size_t outOff, size_t outCap) {
+    size_t const total = cs->flushed + fresh;
+    size_t const oState = ZJ_CS_META, oSrc = oState + cs->stateBytes, oDst = oSrc + cs->window;
+    u64* const h = (u64*)(cs->hPinned + (size_t)slot * ZJ_CS_SLOT_BYTES);
+    h[0] = 0; h[1] = total; h[2] = 0; h[3] = outCap; h[4] = 0; h[5] = 0; h[6] = flushHere ? 1 : 0;
+    ((u32*)(h + 7))[0] = mode; ((u32*)(h + 7))[1] = 0; ((u32*)(h + 8))[0] = (u32)total; ((u32*)(h + 8))[1] = 0;
+    u8* const dv = cs->dBuf; u8* const ds = dv + (size_t)slot * ZJ_CS_SLOT_BYTES;
+    if (hipMemcpyAsync(ds, h, 72, hipMemcpyHostToDevice, cs->st) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (fresh && hipMemcpyAsync(dv + oSrc + cs->flushed, cs->hPinned + ZJ_CS_META + cs->flushed, fresh, hipMemcpyHostToDevice, cs->st) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    return zjni_compress_stream_continue_batch_device(dv + oSrc, (const u64*)ds, dv + oDst + outOff, (const u64*)(ds + 16), (u64*)(ds + 32), 1, cs->level, cs->checksum,
+                                                      (const u32*)(ds + 64), (const u64*)(ds + 40), (const u32*)(ds + 56), dv + oState, cs->st);
+}
+// eager: wait for the pieces in flight and read their sizes.  0, or the code the handle is dead with.
+static size_t zj_cstream_collect(zjni_cstream* cs) {
+    if (!cs->inFlight) return 0;
+    if (hipStreamSynchronize(cs->st) != hipSuccess) return zj_cstream_kill(cs, ZJNI_ERR(ZJNI_ERROR_no_device));
+    for (u32 k = cs->nParts - cs->inFlight; k < cs->nParts; k++) {
+        size_t const out = (size_t)((const u64*)(cs->hPinned + (size_t)k * ZJ_CS_SLOT_BYTES))[4];
+        if (zjni_isError(out)) return zj_cstream_kill(cs, out);
+        if (out > cs->parts[k].cap) return zj_cstream_kill(cs, ZJNI_ERR(70));
+        cs->parts[k].size = out;
+    }
+    cs->inFlight = 0;
+    return 0;
+}
+// eager: frame bytes of parts [firstPart, upTo) that have not been handed out (all of them collected)
+static size_t zj_cstream_held(const zjni_cstream* cs, u32 upTo) {
+    size_t held = 0;
+    for (u32 k = cs->firstPart; k < upTo; k++) held += cs->parts[k].size - cs->parts[k].given;
+    return held;
+}
+// eager: hand out what parts [firstPart, upTo) hold, oldest first, as far as dstCap allows; the rest stays held
+static size_t zj_cstream_hand_out(zjni_cstream* cs, u8* dst, size_t dstCap, u32 upTo) {
+    size_t at = 0;
+    u8 const* const hOut = cs->hPinned + ZJ_CS_META + cs->window;
+    while (cs->firstPart < upTo) {
+        zjni_cstream::Part& p = cs->parts[cs->firstPart];
+        size_t const n = p.size - p.given < dstCap - at ? p.size - p.given : dstCap - at;
+        if (n) memcpy(dst + at, hOut + p.off + p.given, n);
+        p.given += n; at += n;
+        if (p.given < p.size) break;
+        cs->firstPart++;
+    }
+    if (cs->firstPart == cs->nParts) { cs->nParts = 0; cs->firstPart = 0; cs->outCursor = 0; }       // nothing held, nothing in flight: the slots and the area start again
+    return at;
+}
+size_t zjni_cstream_pending(const zjni_cstream* cs) {
+    if (!cs || !cs->eager || cs->dead) return 0;
+    if (cs->inFlight && hipStreamSynchronize(cs->st) != hipSuccess) return 0;
+    size_t held = zj_cstream_held(cs, cs->nParts - cs->inFlight);
+    for (u32 k = cs->nParts - cs->inFlight; k < cs->nParts; k++) {
+        size_t const out = (size_t)((const u64*)(cs->hPinned + (size_t)k * ZJ_CS_SLOT_BYTES))[4];
+        if (!zjni_isError(out)) held += out;
+    }
+    return held;
 }
 size_t zjni_cstream_compress(zjni_cstream* cs, void* dst, size_t dstCap, const void* src, size_t srcSize, int directive) {
     if (!cs || (srcSize && !src) || (dstCap && !dst)) return ZJNI_ERR(72);
@@ -2714,34 +2791,50 @@ size_t zjni_cstream_compress(zjni_cstream* cs, void* dst, size_t dstCap, const v
     if (cs->ordinal != t_dev && t_dev >= 0) return ZJNI_ERR(32);                          // made on another device
     if (cs->dead) return cs->dead;
     if (cs->closed) return cs->dead = ZJNI_ERR(60);
-    if (srcSize > cs->window || cs->flushed + cs->pending + srcSize > cs->window) return cs->dead = ZJNI_ERR(201);      // beyond the window: the caller's CPU path replays the stream
-    if (directive != 0 && dstCap < zj_cstream_bound(cs->pending + srcSize, 1)) return ZJNI_ERR(70);                     // (nothing was touched: the call may be made again with more room)
+    if (srcSize > cs->window || cs->flushed + cs->pending + srcSize > cs->window) return zj_cstream_kill(cs, ZJNI_ERR(201));      // beyond the window: the caller's CPU path replays the stream from byte 0, so what is held is dropped
+    if (zjni_isError(zj_cstream_collect(cs))) return cs->dead;                              // eager: the work of earlier calls
+    size_t const held = zj_cstream_held(cs, cs->nParts);
+    if (directive != 0 && dstCap < held + zj_cstream_bound(cs->pending + srcSize, 1)) return ZJNI_ERR(70);              // (nothing was touched: the call may be made again with more room)
     bool const knownEmpty = directive == 2 && !cs->touched && srcSize == 0;
     cs->touched = true;
-    if (srcSize) memcpy(cs->hPinned + 256 + cs->pending, src, srcSize);
+    if (srcSize) memcpy(cs->hPinned + ZJ_CS_META + cs->flushed + cs->pending, src, srcSize);
     cs->pending += srcSize;
-    if (directive == 0) return 0;                                                           // buffered until a flush
-    size_t const total = cs->flushed + cs->pending;
-    size_t const oState = 256, oSrc = oState + cs->stateBytes, oDst = oSrc + cs->window;
-    u64* const h = (u64*)cs->hPinned;
-    h[0] = 0; h[1] = total; h[2] = 0; h[3] = cs->outCap; h[4] = 0; h[5] = 0; h[6] = directive == 1 ? 1 : 0;
-    ((u32*)(h + 7))[0] = (directive == 2 ? 1u : 0u) | (knownEmpty ? 2u : 0u); ((u32*)(h + 7))[1] = 0; ((u32*)(h + 8))[0] = (u32)total; ((u32*)(h + 8))[1] = 0;
     u8* const dv = cs->dBuf;
+    size_t const oDst = ZJ_CS_META + cs->stateBytes + cs->window;
+    u8* const hOut = cs->hPinned + ZJ_CS_META + cs->window;
+    if (directive == 0) {
+        if (!cs->eager) return 0;                                                           // buffered until a flush
+        u32 const earlier = cs->nParts;
+        size_t const full = cs->pending & ~(size_t)131071;                                  // cs->flushed stands on a piece boundary: the pieces these bytes complete go out now
+        if (full) {
+            size_t const cap = zj_cstream_bound(full, 1);
+            if (cs->nParts == ZJ_CS_SLOTS || cs->outCursor + cap > cs->outCap) return zj_cstream_kill(cs, ZJNI_ERR(1));
+            u32 const k = cs->nParts;
+            u8* const ds = dv + (size_t)k * ZJ_CS_SLOT_BYTES;
+            size_t const r = zj_cstream_launch(cs, k, full, 4u, false, cs->outCursor, cap);
+            if (zjni_isError(r)) return zj_cstream_kill(cs, r);
+            if (hipMemcpyAsync(cs->hPinned + (size_t)k * ZJ_CS_SLOT_BYTES + 32, ds + 32, 8, hipMemcpyDeviceToHost, cs->st) != hipSuccess
+                || hipMemcpyAsync(hOut + cs->outCursor, dv + oDst + cs->outCursor, cap, hipMemcpyDeviceToHost, cs->st) != hipSuccess) return zj_cstream_kill(cs, ZJNI_ERR(ZJNI_ERROR_no_device));
+            cs->parts[k].off = cs->outCursor; cs->parts[k].cap = cap; cs->parts[k].size = 0; cs->parts[k].given = 0;
+            cs->nParts++; cs->inFlight = 1; cs->outCursor += cap;
+            cs->flushed += full; cs->pending -= full;
+        }
+        return zj_cstream_hand_out(cs, (u8*)dst, dstCap, earlier);                          // the frame bytes of earlier calls' pieces; this call's piece is on its way
+    }
+    size_t const given = zj_cstream_hand_out(cs, (u8*)dst, dstCap, cs->nParts);              // eager: everything held goes first (there is room for it)
+    size_t const total = cs->flushed + cs->pending;
+    u64* const h = (u64*)cs->hPinned;
     auto fail = [&](size_t code) { (void)hipStreamSynchronize(cs->st); return cs->dead = code; };
-    if (hipMemcpyAsync(dv, h, 72, hipMemcpyHostToDevice, cs->st) != hipSuccess) return fail(ZJNI_ERR(ZJNI_ERROR_no_device));
-    if (cs->pending && hipMemcpyAsync(dv + oSrc + cs->flushed, cs->hPinned + 256, cs->pending, hipMemcpyHostToDevice, cs->st) != hipSuccess) return fail(ZJNI_ERR(ZJNI_ERROR_no_device));
-    size_t const r = zjni_compress_stream_continue_batch_device(dv + oSrc, (const u64*)dv, dv + oDst, (const u64*)(dv + 16), (u64*)(dv + 32), 1, cs->level, cs->checksum,
-                                                                (const u32*)(dv + 64), (const u64*)(dv + 40), (const u32*)(dv + 56), dv + oState, cs->st);
+    size_t const r = zj_cstream_launch(cs, 0, cs->pending, (directive == 2 ? 1u : 0u) | (knownEmpty ? 2u : 0u), directive == 1, 0, cs->outCap);
     if (zjni_isError(r)) return fail(r);
     if (hipMemcpyAsync(h + 4, dv + 32, 8, hipMemcpyDeviceToHost, cs->st) != hipSuccess || hipStreamSynchronize(cs->st) != hipSuccess) return fail(ZJNI_ERR(ZJNI_ERROR_no_device));
     size_t const out = (size_t)h[4];
     if (zjni_isError(out)) return cs->dead = out;
-    if (out > dstCap || out > cs->outCap) return cs->dead = ZJNI_ERR(70);
-    u8* const hOut = cs->hPinned + 256 + cs->window;
+    if (out > dstCap - given || out > cs->outCap) return cs->dead = ZJNI_ERR(70);
     if (out && (hipMemcpyAsync(hOut, dv + oDst, out, hipMemcpyDeviceToHost, cs->st) != hipSuccess || hipStreamSynchronize(cs->st) != hipSuccess)) return fail(ZJNI_ERR(ZJNI_ERROR_no_device));
-    if (out) memcpy(dst, hOut, out);
+    if (out) memcpy((u8*)dst + given, hOut, out);
     cs->flushed = total; cs->pending = 0; cs->closed = directive == 2;
-    return out;
+    return given + out;
 }
 // ZstdCompressCtx.setHashLog / setChainLog (ZSTD_c_hashLog / ZSTD_c_chainLog; 0 = the library's choice) on top of level + checksum.
 // Honoured for level 3 (double-fast), hashLog 6..17, chainLog 6..16: with 16 / 15 the frames are the reference's plain level 3.
