@@ -161,6 +161,51 @@ size_t zjni_decompress_batch_device_sized(const void* d_src, const uint64_t* d_s
                                           uint64_t slotMax, zjni_frame_info* d_info, uint64_t* d_dst_off, uint64_t* d_needed,
                                           uint64_t* d_result, size_t n, const zjni_ddict* ddict, void* stream);
 
+/* ---- large buffers as many frames ----
+ * The batch entries above are built for many small independent buffers: a buffer of concatenated frames is decoded by ONE wavefront, frame after frame, and an
+ * input above ZJNI_FRAME_MAX is not compressed at all.  zstd's own way to make large data parallel without leaving the format is to cut it into independent
+ * frames laid end to end (pzstd, the seekable format, a log of appended frames, zjni_pack_batch_device2's output); every zstd decoder reads the result as one
+ * buffer (ZSTD_decompressMultiFrame, N/decompress/zstd_decompress.c:1070-1168).  The entries below turn n large buffers into E small entries on the device, run
+ * the batch pipelines above on the entries and fold their answers back into one per buffer.
+ *
+ * Frame-parallel decompress.  zjni_decompress_frames_batch_device takes the arguments, layout, ordering and result convention of
+ * zjni_decompress_batch_device_usingDDict and answers, for every input, valid or not, what that entry answers: the same d_result[i] and, where that is a
+ * size, the same bytes under d_dst.  Split rule: buffer i becomes one entry per frame when (a) its source is at most 2^32 - 1 bytes, (b) a walk over its frame
+ * and block headers from byte 0 until no byte is left meets no error, (c) every zstd frame on the way records a content size and (d) there are at least two zstd
+ * frames; any other buffer is one entry, the whole buffer, exactly as in the entry above.  A skippable frame of a split buffer is an entry that decodes to 0 bytes.
+ * An entry's destination starts at the buffer's slot plus the content sizes before it, clamped to the slot's end: an interior frame's slot is exactly its content
+ * size, the last one keeps the rest, and a buffer that does not fit gets short slots (the decoder answers ZSTD_error_dstSize_tooSmall by itself).  d_result[i] is the
+ * sum of the entries' sizes; a split buffer with an entry that answered an error (damage the header walk cannot see, a wrong dictionary, a short slot) is decoded
+ * again as a whole by the wave-per-buffer kernel over the caller's own offsets, and whatever that answers stands — so no rule of ZSTD_decompressMultiFrame is
+ * restated here.  Asynchronous on `stream` except for one read-back: the host waits for the entry count E (eight bytes, behind the counting walk), because the
+ * pipelines size their launches and scratch on the host.  The entry arrays live in the library's scratch (zjni_set_scratch_limit).  E above 2^32 - 1: 72, as for n.
+ * n == 0 is legal.  With zjni_inspect_batch_device + zjni_decompress_offsets_device in front, this entry also serves callers who hold frames only (no d_dst_off).
+ * zjni_last_frames (synchronises; diagnostics): out4[0] buffers split, out4[1] entries decoded, out4[2] buffers not split, out4[3] buffers decoded again as a
+ * whole, of the last zjni_decompress_frames_batch_device on this device.
+ *
+ * Chunked compress.  zjni_compress_chunked_batch_device writes buffer i as max(1, ceil(size / chunkSize)) frames laid end to end from d_dst + d_dst_off[i]: frame
+ * k is, byte for byte, the frame zjni_compress_batch_device2 writes for src[k * chunkSize, min((k + 1) * chunkSize, size)) into a zjni_compressBound destination
+ * (ZSTD_compress2's frame for that piece at that level); an empty buffer is the one frame of an empty input.  d_result[i] is the total; ZSTD_error_dstSize_tooSmall
+ * (70) when the total exceeds the slot — then nothing is written outside the slot; or, when a piece answers an error (201 / 42 for a level that does not serve
+ * its size), the first such piece's code.  chunkSize: 256 .. ZJNI_BLOCKSIZE_MAX, anything else is ZSTD_error_parameter_outOfBound (42) as the call's return value —
+ * every piece is a single-block frame on the fast routes.  Levels: whatever zjni_compress_batch_device2 serves at the piece's size, negative levels included; no
+ * dictionary, no explicit table sizes.  zjni_compressBound_chunked(srcSize, chunkSize) = the sum of zjni_compressBound over the pieces: a slot of that size always
+ * fits (42 for a chunkSize out of range).  The same one read-back of E as above; E above 2^32 - 1: 72.  The pieces' scratch destinations count as library scratch
+ * and are sliced under zjni_set_scratch_limit.
+ *
+ * zjni_compress_chunked / zjni_decompress_frames: blocking forms for ONE host buffer, staged through pinned memory like zjni_compress2 / zjni_decompress; what
+ * a per-buffer native binds for inputs above ZJNI_FRAME_MAX and for buffers of many frames. */
+size_t zjni_decompress_frames_batch_device(const void* d_src, const uint64_t* d_src_off,
+                                           void* d_dst, const uint64_t* d_dst_off,
+                                           uint64_t* d_result, size_t n, const zjni_ddict* ddict /* may be NULL */, void* stream);
+int zjni_last_frames(unsigned out4[4]);
+size_t zjni_compressBound_chunked(size_t srcSize, size_t chunkSize);
+size_t zjni_compress_chunked_batch_device(const void* d_src, const uint64_t* d_src_off,
+                                          void* d_dst, const uint64_t* d_dst_off,
+                                          uint64_t* d_result, size_t n, int level, int checksum, size_t chunkSize, void* stream);
+size_t zjni_compress_chunked(void* dst, size_t dstCapacity, const void* src, size_t srcSize, int level, int checksum, size_t chunkSize);
+size_t zjni_decompress_frames(void* dst, size_t dstCapacity, const void* src, size_t srcSize);
+
 /* ---- explicit table sizes: ZstdCompressCtx.setHashLog / setChainLog (J/ZstdCompressCtx.java; N/jni_fast_zstd.c setHashLog0 /
  * setChainLog0 -> ZSTD_c_hashLog / ZSTD_c_chainLog) on top of level + checksum; 0 = not set.  Honoured for level 3
  * (double-fast): hashLog 6..17, chainLog 6..16, frames byte-identical to the reference called with the same two

@@ -229,6 +229,19 @@ def lib():
         L.zjni_decompress_offsets_device.argtypes = [vp, sz, C.c_uint64, C.c_uint64, C.c_uint64, vp, vp, vp]
         L.zjni_decompress_batch_device_sized.restype = sz
         L.zjni_decompress_batch_device_sized.argtypes = [vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint64, vp, vp, vp, vp, sz, vp, vp]
+    if hasattr(L, "zjni_decompress_frames_batch_device"):      # large buffers as many frames
+        L.zjni_decompress_frames_batch_device.restype = sz
+        L.zjni_decompress_frames_batch_device.argtypes = [vp, vp, vp, vp, vp, sz, vp, vp]
+        L.zjni_last_frames.restype = C.c_int
+        L.zjni_last_frames.argtypes = [C.POINTER(C.c_uint)]
+        L.zjni_compressBound_chunked.restype = sz
+        L.zjni_compressBound_chunked.argtypes = [sz, sz]
+        L.zjni_compress_chunked_batch_device.restype = sz
+        L.zjni_compress_chunked_batch_device.argtypes = [vp, vp, vp, vp, vp, sz, C.c_int, C.c_int, sz, vp]
+        L.zjni_compress_chunked.restype = sz
+        L.zjni_compress_chunked.argtypes = [vp, sz, vp, sz, C.c_int, C.c_int, sz]
+        L.zjni_decompress_frames.restype = sz
+        L.zjni_decompress_frames.argtypes = [vp, sz, vp, sz]
     _lib = L
     return L
 
@@ -250,7 +263,9 @@ EXPORTS = ("zjni_version", "zjni_device_count", "zjni_init", "zjni_shutdown", "z
            "zjni_compress_batch_begin", "zjni_decompress_batch_begin", "zjni_batch_finish", "zjni_pack_batch_device2",
            "zjni_inspect", "zjni_inspect_batch_device", "zjni_decompress_offsets_device", "zjni_decompress_batch_device_sized",
            "zjni_cstream_state_bytes", "zjni_compress_stream_continue_batch_device", "zjni_createCStream", "zjni_freeCStream", "zjni_cstream_reset", "zjni_cstream_compress",
-           "zjni_createCStream2", "zjni_cstream_pending")
+           "zjni_createCStream2", "zjni_cstream_pending",
+           "zjni_decompress_frames_batch_device", "zjni_last_frames", "zjni_compressBound_chunked", "zjni_compress_chunked_batch_device",
+           "zjni_compress_chunked", "zjni_decompress_frames")
 
 
 # --------------------------------------------------------------------------- Java API mirror --

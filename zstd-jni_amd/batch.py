@@ -134,6 +134,63 @@ def decompress_sized(src_blob, src_off, dst_blob=None, dictionary=None, align=1,
     return dst_blob, dst_off, results, total
 
 
+def compress_bound_chunked(size, chunk):
+    """zjni_compressBound_chunked: the sum of zjni_compressBound over the max(1, ceil(size / chunk)) pieces of a buffer — a slot that always fits."""
+    r = lib().zjni_compressBound_chunked(size, chunk)
+    _check(r)
+    return r
+
+
+def compress_chunked(src_blob, src_off, dst_blob=None, dst_off=None, level=3, checksum=False, chunk=1 << 16, results=None):
+    """Enqueue zjni_compress_chunked_batch_device on the current stream: buffer i becomes max(1, ceil(size / chunk)) independent frames laid end to end
+    in its slot — each the frame compress() writes for that piece — which every zstd decoder reads as one buffer; buffers of any size, `chunk` from 256
+    to 131072 bytes.  Returns (dst_blob, dst_off int64[n + 1], results int64[n]): results[i] is the total, -70 when it exceeds the slot, or the first
+    piece's error.  Without a dst_blob the slots are compress_bound_chunked-sized (src_off is read on the host for that: one wait).  The library itself
+    waits once per call for the number of pieces."""
+    n = src_off.numel() - 1
+    dev = src_blob.device
+    if dst_blob is None:
+        sizes = (src_off[1:] - src_off[:-1]).clamp(min=0).cpu().tolist()
+        offs = [0]
+        for s in sizes:
+            offs.append(offs[-1] + compress_bound_chunked(s, chunk))
+        dst_off = torch.tensor(offs, dtype=torch.int64, device=dev)
+        dst_blob = torch.empty(max(offs[-1], 1), dtype=torch.uint8, device=dev)[:offs[-1]]
+    elif dst_off is None:
+        raise ValueError("compress_chunked: a dst_blob needs its dst_off")
+    if results is None:
+        results = torch.empty(n, dtype=torch.int64, device=dev)
+    _check(lib().zjni_compress_chunked_batch_device(src_blob.data_ptr(), src_off.data_ptr(), dst_blob.data_ptr(), dst_off.data_ptr(), results.data_ptr(), n,
+                                                    level, 1 if checksum else 0, chunk, _stream_ptr()))
+    return dst_blob, dst_off, results
+
+
+def decompress_frames(src_blob, src_off, dst_blob, dst_off, results=None, dictionary=None):
+    """Enqueue zjni_decompress_frames_batch_device on the current stream: decompress() for buffers of MANY concatenated frames (compress_chunked's output,
+    pzstd, appended logs).  A buffer of at least two zstd frames that all record their content size is decoded one frame per wave slot instead of frame
+    after frame by one wave; any other buffer takes decompress()'s route.  Same arguments, same results, same bytes as decompress().  The library waits
+    once per call for the number of frames.  last_frames() says how the last call went."""
+    n = src_off.numel() - 1
+    if results is None:
+        results = torch.empty(n, dtype=torch.int64, device=src_blob.device)
+    dd = dictionary._ptr if dictionary is not None else None
+    _check(lib().zjni_decompress_frames_batch_device(src_blob.data_ptr(), src_off.data_ptr(), dst_blob.data_ptr(), dst_off.data_ptr(),
+                                                     results.data_ptr(), n, dd, _stream_ptr()))
+    return results
+
+
+def last_frames():
+    """zjni_last_frames (synchronises): {"split": buffers decoded frame by frame, "entries": frames and whole buffers handed to the decoder, "unsplit":
+    buffers decoded as one entry, "redo": split buffers decoded again as a whole because one of their frames answered an error} of the last
+    decompress_frames() on this device."""
+    import ctypes as C
+    out = (C.c_uint * 4)()
+    r = lib().zjni_last_frames(out)
+    if r != 0:
+        raise ZstdException(-r, "zjni_last_frames failed")
+    return dict(zip(("split", "entries", "unsplit", "redo"), [int(x) for x in out]))
+
+
 def stream_states(n, level, device="cuda"):
     """n compress-stream states of zjni_cstream_state_bytes(level) bytes each, zeroed: streams on which nothing has been done."""
     size = lib().zjni_cstream_state_bytes(level)

@@ -31,6 +31,7 @@
 #include "zj_match_wave.h"
 #include "zj_synth.h"
 #include "zj_frameinfo.h"
+#include "zj_frames.h"
 
 #define ZJNI_ERR(code) ((size_t)0 - (size_t)(code))
 
@@ -1279,6 +1280,12 @@ struct DevState {
     u8* dlitBuf = nullptr; size_t dlitBufCap = 0;      // literal slots of the split decode pipeline (stage 2b), one per frame of a slice
     u8* dmbBuf = nullptr; size_t dmbBufCap = 0;        // multi-block frames on the split pipeline: [block tables][blocks][frames][seq list][list M][record pool]
     u64* slotPart = nullptr; size_t slotPartCap = 0;   // zjni_decompress_offsets_device: one partial sum per 1 024 buffers (8 B each; not counted as pipeline scratch)
+    // large buffers as many frames (zj_frames.h): the per-buffer and per-entry arrays of zjni_decompress_frames_batch_device / zjni_compress_chunked_batch_device and the
+    // chunked compress's scratch destinations; counts as scratch, but is not evicted by scratch_free_all (the pipelines run inside these calls, which hold it)
+    u8* framesBuf = nullptr; size_t framesBufCap = 0;
+    u32* framesStat = nullptr;                         // device: [0] buffers split, [1] not split, [2] buffers on the redo list, [3] work counter of the redo launch
+    volatile u64* framesE = nullptr; hipEvent_t evFramesE = nullptr;      // pinned: the entry count of the running call, valid behind evFramesE
+    u64 lastFramesE = 0;                               // entries the last zjni_decompress_frames_batch_device decoded (zjni_last_frames)
 };
 std::mutex g_mu;        // guards g_dev
 std::vector<DevState> g_dev;
@@ -1371,7 +1378,7 @@ DevState* cur_state() {
 // has to grow first evicts the other pipelines' buffers (after the device has drained).  0 = no limit (sized for 288 GB).
 size_t g_scratch_limit = 0;
 #define ZJ_SCRATCH_LIMIT_MIN ((size_t)4 << 30)
-size_t scratch_total(const DevState* d) { return d->splitBufCap + d->wideBufCap + d->cdBufCap + d->dsplitBufCap + d->dlitBufCap + d->dmbBufCap; }
+size_t scratch_total(const DevState* d) { return d->splitBufCap + d->wideBufCap + d->cdBufCap + d->dsplitBufCap + d->dlitBufCap + d->dmbBufCap + d->framesBufCap; }
 void scratch_free_all(DevState* d) {
     d->clearedValid = false;                                    // (hipFree drains the device, the clear stream included)
     if (d->splitBuf) (void)hipFree(d->splitBuf); d->splitBuf = nullptr; d->splitBufCap = 0;
@@ -1492,6 +1499,9 @@ void zjni_shutdown(void) {
         if (d.cdBuf) (void)hipFree(d.cdBuf);
         if (d.cdList) (void)hipFree(d.cdList);
         if (d.slotPart) (void)hipFree(d.slotPart);
+        if (d.framesBuf) (void)hipFree(d.framesBuf);
+        if (d.framesStat) (void)hipFree(d.framesStat);
+        if (d.framesE) { (void)hipHostFree((void*)d.framesE); (void)hipEventDestroy(d.evFramesE); }
         for (int p = 0; p < 2; p++) { if (d.cdMatchDone[p]) (void)hipEventDestroy(d.cdMatchDone[p]); if (d.cdEncDone[p]) (void)hipEventDestroy(d.cdEncDone[p]); }
         if (d.sideStream) { (void)hipStreamDestroy(d.sideStream); (void)hipEventDestroy(d.evFork); (void)hipEventDestroy(d.evJoin); }
         if (d.clearStream) { (void)hipStreamDestroy(d.clearStream); (void)hipEventDestroy(d.evMatchDone); (void)hipEventDestroy(d.evCleared); }
@@ -1665,6 +1675,7 @@ size_t zjni_release_scratch(void) {
     std::lock_guard<std::mutex> lk(*d->enqueueMu);              // no batch call is being enqueued ...
     if (hipDeviceSynchronize() != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);   // ... and none is still running
     scratch_free_all(d);
+    if (d->framesBuf) (void)hipFree(d->framesBuf); d->framesBuf = nullptr; d->framesBufCap = 0;
     d->lastValid = false;
     return 0;
 }
@@ -2553,11 +2564,11 @@ static int zj_level3_word(int lw) {
     static int const lds = (zj_tune("ZJNI_L3_TABLES") && !strcmp(zj_tune("ZJNI_L3_TABLES"), "lds")) ? 1 : 0;
     return lds ? lw : (int)(ZE_LW(3u, 16u, 15u) | ZE_LW_IMPLICIT | (w & ~0xFFFFFFu));
 }
-static size_t compress_chunked(const void* d_src, const uint64_t* d_src_off, void* d_dst, const uint64_t* d_dst_off,
-                               uint64_t* d_result, size_t n, int level, u32 flags, void* stream) {
+// (the caller holds the device's BatchOrder)
+static size_t compress_chunked_ordered(const void* d_src, const uint64_t* d_src_off, void* d_dst, const uint64_t* d_dst_off,
+                                       uint64_t* d_result, size_t n, int level, u32 flags, void* stream) {
     level = zj_negative_word(level);              // negative level -> level word (zj_encode.h: ZE_LW_NEG)
     level = zj_level3_word(level);
-    BatchOrder order(cur_state(), stream);
     size_t const perFrame = ZE_LW_LEVEL((u32)level) > 3u ? (size_t)ZE_CHAIN_TABLE_BYTES + ZE_FRAME_STRIDE(ZE_CHAIN_MAX_SRC) + 21
                                                           : (size_t)ze_lane_table_stride((u32)level, false) + ZE_FRAME_STRIDE(65536u) + 21;
     size_t const chunk = scratch_slice(perFrame, ZJ_CHUNK_FRAMES, 2);
@@ -2567,6 +2578,11 @@ static size_t compress_chunked(const void* d_src, const uint64_t* d_src_off, voi
         if (r != 0 || n == 0) return r;
     }
     return 0;
+}
+static size_t compress_chunked(const void* d_src, const uint64_t* d_src_off, void* d_dst, const uint64_t* d_dst_off,
+                               uint64_t* d_result, size_t n, int level, u32 flags, void* stream) {
+    BatchOrder order(cur_state(), stream);
+    return compress_chunked_ordered(d_src, d_src_off, d_dst, d_dst_off, d_result, n, level, flags, stream);
 }
 size_t zjni_compress_batch_device(const void* d_src, const uint64_t* d_src_off, void* d_dst, const uint64_t* d_dst_off,
                                   uint64_t* d_result, size_t n, int level, void* stream) {
@@ -3576,6 +3592,277 @@ size_t zjni_pack_batch_device(const void* d_src, const uint64_t* d_src_off, cons
     hipLaunchKernelGGL(zj_pack_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, (const u8*)d_src, (const u64*)d_src_off,
                        (const u64*)d_sizes, (u8*)d_dst, (const u64*)d_dst_off, (u32)n);
     return hipGetLastError() == hipSuccess ? 0 : ZJNI_ERR(ZJNI_ERROR_no_device);
+}
+
+// ============================================================================ large buffers as many frames (zj_frames.h) ============
+// zjni_decompress_frames_batch_device and zjni_compress_chunked_batch_device turn n large buffers into E small entries on the device, run the existing batch
+// pipelines on the entries and fold the entries' answers back into one per buffer.  No existing kernel changes: the pipelines take their batch size by value and size
+// their scratch on the host, so the one thing the host has to know is E — eight bytes read back through pinned memory behind the count and its scan, the only
+// host wait of either entry.  Everything else follows on `stream` in order.
+//
+// framesBuf holds, per call: the per-buffer arrays (counts, their scans, carries), the per-entry arrays and, for the chunked compress, the entries' scratch
+// destinations of one slice.
+static bool frames_state(DevState* d) {
+    if (!d->framesStat && hipMalloc(&d->framesStat, 64) != hipSuccess) { d->framesStat = nullptr; (void)hipGetLastError(); return false; }
+    if (!d->framesE) {
+        void* hp = nullptr;
+        if (hipHostMalloc(&hp, 64, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return false; }
+        if (hipEventCreateWithFlags(&d->evFramesE, hipEventDisableTiming) != hipSuccess) { (void)hipHostFree(hp); (void)hipGetLastError(); return false; }
+        memset(hp, 0, 64); d->framesE = (volatile u64*)hp;
+    }
+    return true;
+}
+// at least `need` bytes of framesBuf; with keep != 0 the first `keep` bytes survive a move (the per-buffer arrays, written before E was known)
+static size_t frames_room(DevState* d, size_t need, size_t keep, hipStream_t st) {
+    if (d->framesBufCap >= need) return 0;
+    if (g_scratch_limit && need > g_scratch_limit) return ZJNI_ERR(64);
+    size_t const cap = need + (need >> 3) + 4096;
+    u8* fresh = nullptr;
+    if (hipStreamSynchronize(st) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (hipMalloc(&fresh, cap) != hipSuccess) { (void)hipGetLastError(); return ZJNI_ERR(64); }
+    if (keep && hipMemcpy(fresh, d->framesBuf, keep, hipMemcpyDeviceToDevice) != hipSuccess) { (void)hipFree(fresh); return ZJNI_ERR(ZJNI_ERROR_no_device); }
+    if (d->framesBuf) (void)hipFree(d->framesBuf);          // (drains the device: an earlier call may still be reading it)
+    d->framesBuf = fresh; d->framesBufCap = cap;
+    return 0;
+}
+// first[n] (a scan's total = E) -> the host.  The wait is for the count kernel and its scan only (and for whatever the stream held before them).
+static size_t frames_read_total(DevState* d, const u64* d_total, hipStream_t st, u64* out) {
+    if (hipMemcpyAsync((void*)d->framesE, d_total, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipEventRecord(d->evFramesE, st) != hipSuccess
+        || hipEventSynchronize(d->evFramesE) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    *out = d->framesE[0];
+    return 0;
+}
+static inline size_t zj_up16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// ---- frame-parallel decompress ----
+// first walk, one lane per buffer as zj_inspect_kernel walks: cnt[i] = entries of buffer i
+__global__ __launch_bounds__(64) void zj_frames_count_kernel(const u8* __restrict__ src, const u64* __restrict__ off, u64* __restrict__ cnt, u32 n, u32* stat) {
+    u64 const i = (u64)blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    u64 const lo = off[i], hi = off[i + 1];
+    u32 const c = zj_frames_count(src + lo, hi > lo ? hi - lo : 0);
+    cnt[i] = c;
+    atomicAdd(&stat[c > 1u ? 0 : 1], 1u);
+}
+// second walk: the entries of buffer i at first[i]; the lane of the last buffer closes both arrays with the batch's ends
+__global__ __launch_bounds__(64) void zj_frames_emit_kernel(const u8* __restrict__ src, const u64* __restrict__ off, const u64* __restrict__ dstOff, const u64* __restrict__ first,
+                                                            u64* __restrict__ srcOffE, u64* __restrict__ dstOffE, u32 n) {
+    u64 const i = (u64)blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    u64 const lo = off[i], hi = off[i + 1], dlo = dstOff[i], dhi = dstOff[i + 1], e0 = first[i], e1 = first[i + 1];
+    zj_frames_emit(src + lo, hi > lo ? hi - lo : 0, lo, dlo, dhi > dlo ? dhi - dlo : 0, (u32)(e1 - e0), srcOffE + e0, dstOffE + e0);
+    if (i + 1 == n) { srcOffE[e1] = hi; dstOffE[e1] = dhi; }
+}
+// One wave per buffer: the sum of its entries' sizes; a buffer with an entry that answered an error goes on the redo list instead.  A buffer of one entry
+// (not split) takes that entry's answer as it is.
+__global__ __launch_bounds__(64) void zj_frames_reduce_kernel(const u64* __restrict__ first, const u64* __restrict__ resE, u64* __restrict__ result, u32 n,
+                                                              u32* __restrict__ redo, u32* stat) {
+    u32 const lane = threadIdx.x;
+    for (u32 i = blockIdx.x; i < n; i += gridDim.x) {
+        u64 const lo = first[i], hi = first[i + 1];
+        if (hi - lo == 1) { if (lane == 0) result[i] = resE[lo]; continue; }
+        u64 sum = 0; u32 bad = 0;
+        for (u64 e = lo + lane; e < hi; e += 64) { u64 const r = resE[e]; if (r > ((u64)1 << 40)) bad = 1; else sum += r; }
+        for (u32 d = 32; d; d >>= 1) { sum += __shfl_xor(sum, (int)d, 64); bad |= __shfl_xor(bad, (int)d, 64); }
+        if (lane == 0) {
+            if (bad) redo[atomicAdd(&stat[2], 1u)] = i;
+            else result[i] = sum;
+        }
+    }
+}
+size_t zjni_decompress_frames_batch_device(const void* d_src, const uint64_t* d_src_off, void* d_dst, const uint64_t* d_dst_off,
+                                           uint64_t* d_result, size_t n, const zjni_ddict* ddict, void* stream) {
+    if (ddict && ddict->ordinal != t_dev && t_dev >= 0) return ZJNI_ERR(32);      // digested on another device
+    DevState* d = cur_state();
+    if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (n > 0xFFFFFFFFull) return ZJNI_ERR(72);
+    hipStream_t const st = (hipStream_t)stream;
+    BatchOrder order(d, stream);
+    if (!frames_state(d)) return ZJNI_ERR(64);
+    if (hipMemsetAsync(d->framesStat, 0, 16, st) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    d->lastFramesE = 0;
+    if (n == 0) return 0;
+    // per buffer: [cnt n][first n + 1][redo n (u32)]
+    size_t const oCnt = 0, oFirst = zj_up16(n * 8), oRedo = oFirst + zj_up16((n + 1) * 8), perBuf = oRedo + zj_up16(n * 4);
+    size_t r = frames_room(d, perBuf, 0, st);
+    if (r != 0) return r;
+    hipLaunchKernelGGL(zj_frames_count_kernel, dim3((u32)((n + 63) / 64)), dim3(64), 0, st, (const u8*)d_src, (const u64*)d_src_off, (u64*)(d->framesBuf + oCnt), (u32)n, d->framesStat);
+    hipLaunchKernelGGL(zj_pack_offsets_kernel, dim3(1), dim3(1024), 0, st, (const u64*)(d->framesBuf + oCnt), (u64*)(d->framesBuf + oFirst), (u32)n);
+    u64 E = 0;
+    if ((r = frames_read_total(d, (const u64*)(d->framesBuf + oFirst) + n, st, &E)) != 0) return r;
+    if (E > 0xFFFFFFFFull) return ZJNI_ERR(72);
+    if (E < n) return ZJNI_ERR(ZJNI_ERROR_no_device);                           // (every buffer is at least one entry)
+    // per entry: [srcOffE E + 1][dstOffE E + 1][resE E]
+    size_t const oSrcE = perBuf, oDstE = oSrcE + zj_up16((E + 1) * 8), oResE = oDstE + zj_up16((E + 1) * 8), total = oResE + zj_up16(E * 8);
+    if ((r = frames_room(d, total, perBuf, st)) != 0) return r;
+    u8* const fb = d->framesBuf;
+    hipLaunchKernelGGL(zj_frames_emit_kernel, dim3((u32)((n + 63) / 64)), dim3(64), 0, st, (const u8*)d_src, (const u64*)d_src_off, (const u64*)d_dst_off, (const u64*)(fb + oFirst),
+                       (u64*)(fb + oSrcE), (u64*)(fb + oDstE), (u32)n);
+    if (hipGetLastError() != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if ((r = decompress_chunked_ordered(d_src, (const u64*)(fb + oSrcE), d_dst, (const u64*)(fb + oDstE), (u64*)(fb + oResE), (size_t)E, ddict, stream)) != 0) return r;
+    u32 const gridR = (u32)(n < (size_t)d->numCU * 8 ? n : (size_t)d->numCU * 8);
+    hipLaunchKernelGGL(zj_frames_reduce_kernel, dim3(gridR), dim3(64), 0, st, (const u64*)(fb + oFirst), (const u64*)(fb + oResE), (u64*)d_result, (u32)n, (u32*)(fb + oRedo), d->framesStat);
+    // the redo list: the fused kernel over the caller's own offsets, one wave per buffer; whatever it answers stands (an empty list is a launch that finds no work)
+    if (ddict) {
+        u32 const gridD = (u32)(n < (size_t)d->decDictGrid ? n : (size_t)d->decDictGrid);
+        hipLaunchKernelGGL(zj_decode_dict_kernel, dim3(gridD), dim3(64), 0, st, (const u8*)d_src, (const u64*)d_src_off, (u8*)d_dst, (const u64*)d_dst_off, (u64*)d_result, (u32)n,
+                           d->framesStat + 3, d->decScratch, d->prof, (const u32*)(fb + oRedo), (const u32*)(d->framesStat + 2), (const ZDDictDev*)ddict->buf, (const u8*)(ddict->buf + sizeof(ZDDictDev)));
+    } else {
+        u32 const gridD = (u32)(n < (size_t)d->decGrid ? n : (size_t)d->decGrid);
+        hipLaunchKernelGGL(zj_decode_kernel, dim3(gridD), dim3(64), 0, st, (const u8*)d_src, (const u64*)d_src_off, (u8*)d_dst, (const u64*)d_dst_off, (u64*)d_result, (u32)n,
+                           d->framesStat + 3, d->decScratch, d->prof, (const u32*)(fb + oRedo), (const u32*)(d->framesStat + 2), (const ZDDictDev*)nullptr, (const u8*)nullptr);
+    }
+    d->lastFramesE = E;
+    return hipGetLastError() == hipSuccess ? 0 : ZJNI_ERR(ZJNI_ERROR_no_device);
+}
+int zjni_last_frames(unsigned* out4) {
+    DevState* d = cur_state();
+    if (!d || !out4) return -(int)ZJNI_ERROR_no_device;
+    u32 h[4] = {0, 0, 0, 0};
+    if (hipDeviceSynchronize() != hipSuccess || (d->framesStat && hipMemcpy(h, d->framesStat, sizeof h, hipMemcpyDeviceToHost) != hipSuccess)) return -(int)ZJNI_ERROR_no_device;
+    out4[0] = h[0]; out4[1] = (unsigned)d->lastFramesE; out4[2] = h[1]; out4[3] = h[2];
+    return 0;
+}
+
+// ---- chunked compress ----
+size_t zjni_compressBound_chunked(size_t srcSize, size_t chunkSize) {
+    if (chunkSize < 256 || chunkSize > ZJNI_BLOCKSIZE_MAX) return ZJNI_ERR(42);
+    return (size_t)zj_chunk_bound_total(srcSize, chunkSize);
+}
+// one lane per buffer: its pieces and what their scratch destinations take
+__global__ __launch_bounds__(256) void zj_chunks_count_kernel(const u64* __restrict__ off, u32 n, u64 chunk, u64* __restrict__ cnt, u64* __restrict__ btot) {
+    u64 const i = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    u64 const lo = off[i], hi = off[i + 1], size = hi > lo ? hi - lo : 0;
+    cnt[i] = zj_chunk_count(size, chunk);
+    btot[i] = zj_chunk_bound_total(size, chunk);
+}
+// one lane per entry of the slice [a, a + m], its end included: where the piece begins in the source, and in the slice's scratch (relative to the slice's first)
+__global__ __launch_bounds__(256) void zj_chunks_emit_kernel(const u64* __restrict__ off, const u64* __restrict__ first, const u64* __restrict__ bbase, u32 n, u64 chunk,
+                                                             u64 a, u32 m, u64 E, u64* __restrict__ srcOffS, u64* __restrict__ dstOffS) {
+    u64 const j = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (j > m) return;
+    u64 const ia = zj_entry_owner(first, n, a), dstA = zj_chunk_dst(bbase[ia], chunk, a - first[ia]);
+    u64 const e = a + j;
+    if (e >= E) { srcOffS[j] = off[n]; dstOffS[j] = bbase[n] - dstA; return; }
+    u64 const i = zj_entry_owner(first, n, e), k = e - first[i];
+    srcOffS[j] = zj_chunk_src(off[i], chunk, k);
+    dstOffS[j] = zj_chunk_dst(bbase[i], chunk, k) - dstA;
+}
+// One wave per buffer, the entries it has in the slice [a, a + m): a running sum of the frame sizes (carried from slice to slice) places every frame in the caller's
+// slot; a frame moves only when it ends inside the slot, so nothing is written outside it; the first entry that answered an error is remembered.
+__global__ __launch_bounds__(64) void zj_chunks_place_kernel(const u64* __restrict__ first, const u64* __restrict__ dstOff, u32 n, u64 a, u32 m, const u64* __restrict__ resS,
+                                                             u64* __restrict__ carry, u64* __restrict__ ferr, u64* __restrict__ packSize, u64* __restrict__ packDst) {
+    u32 const lane = threadIdx.x;
+    for (u32 i = blockIdx.x; i < n; i += gridDim.x) {
+        u64 const f0 = first[i], f1 = first[i + 1], lo = f0 > a ? f0 : a, hi = f1 < a + m ? f1 : a + m;
+        if (lo >= hi) continue;
+        u64 const dlo = dstOff[i], dhi = dstOff[i + 1], cap = dhi > dlo ? dhi - dlo : 0;
+        u64 run = carry[i], err = ferr[i];
+        for (u64 base = lo; base < hi; base += 64) {
+            u64 const e = base + lane;
+            bool const in = e < hi;
+            u64 const r = in ? resS[e - a] : 0;
+            bool const bad = r > ((u64)1 << 40);
+            u64 const sz = bad ? 0 : r;
+            u64 incl = sz;
+            for (u32 d = 1; d < 64; d <<= 1) { u64 const v = __shfl_up(incl, d, 64); if (lane >= d) incl += v; }
+            u64 const pos = run + (incl - sz);
+            if (in) { packSize[e - a] = (!bad && pos + sz <= cap) ? sz : ~(u64)0; packDst[e - a] = dlo + (pos < cap ? pos : cap); }
+            unsigned long long const mask = __ballot(bad);
+            if (mask && !err) err = __shfl(r, (int)(__ffsll((long long)mask) - 1), 64);
+            run += __shfl(incl, 63, 64);
+        }
+        if (lane == 0) { carry[i] = run; ferr[i] = err; }
+    }
+}
+__global__ __launch_bounds__(256) void zj_chunks_verdict_kernel(const u64* __restrict__ dstOff, u32 n, const u64* __restrict__ carry, const u64* __restrict__ ferr, u64* __restrict__ result) {
+    u64 const i = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    u64 const dlo = dstOff[i], dhi = dstOff[i + 1], cap = dhi > dlo ? dhi - dlo : 0;
+    result[i] = ferr[i] ? ferr[i] : (carry[i] > cap ? ZJ_ERR64(ZJ_E_DSTSIZE_TOO_SMALL) : carry[i]);
+}
+size_t zjni_compress_chunked_batch_device(const void* d_src, const uint64_t* d_src_off, void* d_dst, const uint64_t* d_dst_off,
+                                          uint64_t* d_result, size_t n, int level, int checksum, size_t chunkSize, void* stream) {
+    if (level == 0) level = 3;                    // ZSTD_CLEVEL_DEFAULT, as ZSTD_c_compressionLevel = 0 means
+    if (!zj_level_served(level)) return ZJNI_ERR(42);
+    if (chunkSize < 256 || chunkSize > ZJNI_BLOCKSIZE_MAX) return ZJNI_ERR(42);
+    DevState* d = cur_state();
+    if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (n > 0xFFFFFFFFull) return ZJNI_ERR(72);
+    if (n == 0) return 0;
+    hipStream_t const st = (hipStream_t)stream;
+    BatchOrder order(d, stream);
+    if (!frames_state(d)) return ZJNI_ERR(64);
+    // per buffer: [cnt n][btot n][first n + 1][bbase n + 1][carry n][ferr n]
+    size_t const nb = zj_up16((n + 1) * 8), oCnt = 0, oBtot = nb, oFirst = 2 * nb, oBbase = 3 * nb, oCarry = 4 * nb, oFerr = 5 * nb, perBuf = 6 * nb;
+    size_t r = frames_room(d, perBuf, 0, st);
+    if (r != 0) return r;
+    u32 const gridN = (u32)((n + 255) / 256);
+    hipLaunchKernelGGL(zj_chunks_count_kernel, dim3(gridN), dim3(256), 0, st, (const u64*)d_src_off, (u32)n, (u64)chunkSize, (u64*)(d->framesBuf + oCnt), (u64*)(d->framesBuf + oBtot));
+    hipLaunchKernelGGL(zj_pack_offsets_kernel, dim3(1), dim3(1024), 0, st, (const u64*)(d->framesBuf + oCnt), (u64*)(d->framesBuf + oFirst), (u32)n);
+    hipLaunchKernelGGL(zj_pack_offsets_kernel, dim3(1), dim3(1024), 0, st, (const u64*)(d->framesBuf + oBtot), (u64*)(d->framesBuf + oBbase), (u32)n);
+    if (hipMemsetAsync(d->framesBuf + oCarry, 0, 2 * nb, st) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    u64 E = 0;
+    if ((r = frames_read_total(d, (const u64*)(d->framesBuf + oFirst) + n, st, &E)) != 0) return r;
+    if (E > 0xFFFFFFFFull) return ZJNI_ERR(72);
+    if (E < n) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    // per slice of S entries: [srcOffS S + 1][dstOffS S + 1][resS S][packSize S][packDst S][scratch destinations: S x zjni_compressBound(chunk)]
+    size_t const bound = (size_t)zj_compress_bound(chunkSize);
+    size_t S = scratch_slice(bound + 48, ZJ_CHUNK_FRAMES, 4);
+    if (S > E) S = (size_t)E;
+    size_t const ns = zj_up16((S + 1) * 8), oSrcS = perBuf, oDstS = oSrcS + ns, oResS = oDstS + ns, oPSize = oResS + ns, oPDst = oPSize + ns, oOut = oPDst + ns;
+    size_t const total = oOut + zj_up16(S * bound) + 16;
+    if ((r = frames_room(d, total, perBuf, st)) != 0) return r;
+    u8* const fb = d->framesBuf;
+    u32 const gridW = (u32)(n < (size_t)d->numCU * 8 ? n : (size_t)d->numCU * 8);
+    for (u64 a = 0; a < E; a += S) {
+        u32 const m = (u32)(E - a < S ? E - a : S);
+        hipLaunchKernelGGL(zj_chunks_emit_kernel, dim3(m / 256 + 1), dim3(256), 0, st, (const u64*)d_src_off, (const u64*)(fb + oFirst), (const u64*)(fb + oBbase), (u32)n, (u64)chunkSize,
+                           a, m, E, (u64*)(fb + oSrcS), (u64*)(fb + oDstS));
+        if (hipGetLastError() != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+        if ((r = compress_chunked_ordered(d_src, (const u64*)(fb + oSrcS), fb + oOut, (const u64*)(fb + oDstS), (u64*)(fb + oResS), m, level, checksum ? ZE_FLAG_CHECKSUM : 0u, stream)) != 0) return r;
+        hipLaunchKernelGGL(zj_chunks_place_kernel, dim3(gridW), dim3(64), 0, st, (const u64*)(fb + oFirst), (const u64*)d_dst_off, (u32)n, a, m, (const u64*)(fb + oResS),
+                           (u64*)(fb + oCarry), (u64*)(fb + oFerr), (u64*)(fb + oPSize), (u64*)(fb + oPDst));
+        u32 const gridP = (u32)(m < (u32)d->numCU * 8u ? m : (u32)d->numCU * 8u);
+        hipLaunchKernelGGL(zj_pack_kernel, dim3(gridP), dim3(256), 0, st, (const u8*)(fb + oOut), (const u64*)(fb + oDstS), (const u64*)(fb + oPSize), (u8*)d_dst, (const u64*)(fb + oPDst), m);
+    }
+    hipLaunchKernelGGL(zj_chunks_verdict_kernel, dim3(gridN), dim3(256), 0, st, (const u64*)d_dst_off, (u32)n, (const u64*)(fb + oCarry), (const u64*)(fb + oFerr), (u64*)d_result);
+    return hipGetLastError() == hipSuccess ? 0 : ZJNI_ERR(ZJNI_ERROR_no_device);
+}
+
+// ---- blocking forms for one host buffer, staged like zjni_compress2 / zjni_decompress: [srcOff 2][dstOff 2][result 1][pad][src][dst] in one staging slot ----
+static size_t host_one_buffer(bool compress, void* dst, size_t dstCap, const void* src, size_t srcSize, int level, int checksum, size_t chunkSize) {
+    DevState* d = cur_state();
+    if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (srcSize > ((size_t)1 << 46) || dstCap > ((size_t)1 << 46)) return ZJNI_ERR(64);
+    if ((srcSize && !src) || (dstCap && !dst)) return ZJNI_ERR(72);
+    size_t const oSrc = 64, oDst = oSrc + zj_up16(srcSize), total = oDst + dstCap + 16;
+    SlotLock slotLock(d); StageSlot* const sl = slotLock.s;
+    if (!ensure_staging(sl, total)) return ZJNI_ERR(ZJNI_ERROR_unsupported);
+    hipStream_t const hst = sl->hostK;
+    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drainOnExit{hst};
+    u64* const h = (u64*)sl->hPinned;
+    h[0] = 0; h[1] = srcSize; h[2] = 0; h[3] = dstCap; h[4] = 0;
+    if (srcSize) memcpy(sl->hPinned + oSrc, src, srcSize);
+    if (hipMemcpyAsync(sl->dStage, sl->hPinned, oSrc + srcSize, hipMemcpyHostToDevice, hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    const u64* const dOff = (const u64*)sl->dStage;
+    size_t const r = compress ? zjni_compress_chunked_batch_device(sl->dStage + oSrc, dOff, sl->dStage + oDst, dOff + 2, (u64*)sl->dStage + 4, 1, level, checksum, chunkSize, hst)
+                              : zjni_decompress_frames_batch_device(sl->dStage + oSrc, dOff, sl->dStage + oDst, dOff + 2, (u64*)sl->dStage + 4, 1, nullptr, hst);
+    if (zjni_isError(r)) return r;
+    if (hipMemcpyAsync(sl->hPinned + 32, sl->dStage + 32, 8, hipMemcpyDeviceToHost, hst) != hipSuccess || hipStreamSynchronize(hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    size_t const res = (size_t)h[4];
+    if (zjni_isError(res) || res == 0) return res;
+    if (res > dstCap) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (hipMemcpyAsync(sl->hPinned + oDst, sl->dStage + oDst, res, hipMemcpyDeviceToHost, hst) != hipSuccess || hipStreamSynchronize(hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    memcpy(dst, sl->hPinned + oDst, res);
+    return res;
+}
+size_t zjni_compress_chunked(void* dst, size_t dstCap, const void* src, size_t srcSize, int level, int checksum, size_t chunkSize) {
+    return host_one_buffer(true, dst, dstCap, src, srcSize, level, checksum, chunkSize);
+}
+size_t zjni_decompress_frames(void* dst, size_t dstCap, const void* src, size_t srcSize) {
+    return host_one_buffer(false, dst, dstCap, src, srcSize, 0, 0, 0);
 }
 
 }  // extern "C"
