@@ -206,6 +206,41 @@ size_t zjni_compress_chunked_batch_device(const void* d_src, const uint64_t* d_s
 size_t zjni_compress_chunked(void* dst, size_t dstCapacity, const void* src, size_t srcSize, int level, int checksum, size_t chunkSize);
 size_t zjni_decompress_frames(void* dst, size_t dstCapacity, const void* src, size_t srcSize);
 
+/* ---- ranged decompress: decode only the frames a byte range touches ----
+ * A buffer of many frames allows random access: a reader who wants decoded bytes [lo, lo + len) of buffer i needs the frames that hold them and no others.
+ * zjni_decompress_frames_range_batch_device takes the layout, ordering and result convention of zjni_decompress_frames_batch_device plus d_range[2n] = (lo_i,
+ * len_i), in decoded bytes of buffer i.  A buffer is decided in this order; the first rule that applies answers for it.
+ *  1. Not indexable.  The buffer is walked frame header by frame header from byte 0 until no byte is left.  A walk that meets an error answers that step's own
+ *     code (what ZSTD_findFrameCompressedSize answers at that frame); a zstd frame without a content size, a source above 2^32 - 1 bytes and content sizes that
+ *     sum past 64 bits answer ZSTD_error_frameParameter_unsupported (14); of these, whichever the walk meets first.  One frame is enough.  d_total[i] = ~0 - 1.
+ *  2. Range clamp.  T = the sum of the recorded content sizes (a skippable frame counts 0); d_total[i] = T.  lo' = min(lo, T), hi' = min(lo + len, T) with a
+ *     saturating sum.  lo' == hi': the result is 0, nothing is decoded or written.
+ *  3. Slot.  A slot d_dst_off[i + 1] - d_dst_off[i] (0 when not ascending) below hi' - lo' answers 70; nothing is decoded or written.
+ *  4. Selection.  `first` is the frame holding decoded byte lo', `last` the one holding byte hi' - 1.  Every frame from first to last is decoded, frames without
+ *     content and skippable frames between them included.  NO OTHER FRAME IS DECODED: damage outside the selection, which a decode of the whole buffer would
+ *     report, is not seen — as with any seekable reader, a range answers for the frames it touches only.  first is an EDGE when it begins before lo', last when
+ *     it ends after hi' (they may be one frame); an edge frame is decoded into library scratch and its part copied out, so an edge frame whose content size
+ *     exceeds ZJNI_RANGE_EDGE_MAX answers ZSTD_error_memory_allocation (64) and nothing is decoded.  All other selected frames decode straight into the slot.
+ *  5. Answer.  hi' - lo', with exactly the bytes [lo', hi') of the buffer's decoded content at d_dst + d_dst_off[i] and no other byte of d_dst written.  When
+ *     selected frames answer errors, the result is the code of the lowest-numbered such frame, where a frame's answer is what
+ *     zjni_decompress_batch_device_usingDDict gives for that frame alone with a capacity of exactly its content size; bytes inside the first hi' - lo' bytes of
+ *     the slot are then unspecified, and nothing outside them is written.
+ * Asynchronous on `stream` except for one read-back of 40 bytes behind the counting walk (entry counts and scratch sizes: the pipelines size their launches on the
+ * host).  The selected source bytes, the entry arrays and the edge frames' scratch live in the library's scratch (zjni_set_scratch_limit: 64 above it).
+ * n == 0 is legal; n or an entry count above 2^32 - 1: 72; a ddict digested on another device: 32.  d_total may be NULL.
+ * zjni_last_frames_range (synchronises; diagnostics) of the last ranged call on this device: out4[0] buffers served (rules 2-5 reached without an error), out4[1]
+ * frames handed to the decoder, out4[2] edge frames among them, out4[3] buffers that answered an error.
+ * zjni_decompress_frames_range: the blocking form for ONE host buffer, staged like zjni_decompress_frames; *total (may be NULL) receives d_total's value. */
+#define ZJNI_RANGE_EDGE_MAX ((size_t)128 << 20)
+size_t zjni_decompress_frames_range_batch_device(const void* d_src, const uint64_t* d_src_off,
+                                                 void* d_dst, const uint64_t* d_dst_off,
+                                                 const uint64_t* d_range /* [2n]: lo_i, len_i, in decoded bytes of buffer i */,
+                                                 uint64_t* d_result, uint64_t* d_total /* [n] or NULL */, size_t n,
+                                                 const zjni_ddict* ddict /* may be NULL */, void* stream);
+int zjni_last_frames_range(unsigned out4[4]);
+size_t zjni_decompress_frames_range(void* dst, size_t dstCapacity, const void* src, size_t srcSize,
+                                    unsigned long long lo, unsigned long long len, unsigned long long* total /* or NULL */);
+
 /* ---- explicit table sizes: ZstdCompressCtx.setHashLog / setChainLog (J/ZstdCompressCtx.java; N/jni_fast_zstd.c setHashLog0 /
  * setChainLog0 -> ZSTD_c_hashLog / ZSTD_c_chainLog) on top of level + checksum; 0 = not set.  Honoured for level 3
  * (double-fast): hashLog 6..17, chainLog 6..16, frames byte-identical to the reference called with the same two

@@ -242,6 +242,13 @@ def lib():
         L.zjni_compress_chunked.argtypes = [vp, sz, vp, sz, C.c_int, C.c_int, sz]
         L.zjni_decompress_frames.restype = sz
         L.zjni_decompress_frames.argtypes = [vp, sz, vp, sz]
+    if hasattr(L, "zjni_decompress_frames_range_batch_device"):      # ranged decompress
+        L.zjni_decompress_frames_range_batch_device.restype = sz
+        L.zjni_decompress_frames_range_batch_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]
+        L.zjni_last_frames_range.restype = C.c_int
+        L.zjni_last_frames_range.argtypes = [C.POINTER(C.c_uint)]
+        L.zjni_decompress_frames_range.restype = sz
+        L.zjni_decompress_frames_range.argtypes = [vp, sz, vp, sz, C.c_ulonglong, C.c_ulonglong, C.POINTER(C.c_ulonglong)]
     _lib = L
     return L
 
@@ -265,7 +272,8 @@ EXPORTS = ("zjni_version", "zjni_device_count", "zjni_init", "zjni_shutdown", "z
            "zjni_cstream_state_bytes", "zjni_compress_stream_continue_batch_device", "zjni_createCStream", "zjni_freeCStream", "zjni_cstream_reset", "zjni_cstream_compress",
            "zjni_createCStream2", "zjni_cstream_pending",
            "zjni_decompress_frames_batch_device", "zjni_last_frames", "zjni_compressBound_chunked", "zjni_compress_chunked_batch_device",
-           "zjni_compress_chunked", "zjni_decompress_frames")
+           "zjni_compress_chunked", "zjni_decompress_frames",
+           "zjni_decompress_frames_range_batch_device", "zjni_last_frames_range", "zjni_decompress_frames_range")
 
 
 # --------------------------------------------------------------------------- Java API mirror --

@@ -191,6 +191,36 @@ def last_frames():
     return dict(zip(("split", "entries", "unsplit", "redo"), [int(x) for x in out]))
 
 
+def decompress_frames_range(src_blob, src_off, dst_blob, dst_off, ranges, results=None, totals=None, dictionary=None):
+    """Enqueue zjni_decompress_frames_range_batch_device on the current stream: of buffer i (many concatenated frames that all record their content size) decode
+    only the frames that hold the decoded bytes [lo_i, lo_i + len_i) and leave exactly those bytes, clamped to the buffer's content, at dst_off[i].  `ranges` is an
+    int64[n, 2] (or [2n]) tensor of (lo, len).  Returns (results int64[n], totals int64[n]): the bytes written or a negative error code, and the buffer's whole
+    decoded size (-2 when it cannot be indexed).  Damage in frames outside the range is not seen.  The library waits once per call for the entry counts.
+    last_frames_range() says how the last call went."""
+    n = src_off.numel() - 1
+    if ranges.dtype != torch.int64 or not ranges.is_contiguous() or ranges.numel() != 2 * n:
+        raise ValueError("decompress_frames_range: ranges must be a contiguous int64 tensor of n (lo, len) pairs")
+    if results is None:
+        results = torch.empty(n, dtype=torch.int64, device=src_blob.device)
+    if totals is None:
+        totals = torch.empty(n, dtype=torch.int64, device=src_blob.device)
+    dd = dictionary._ptr if dictionary is not None else None
+    _check(lib().zjni_decompress_frames_range_batch_device(src_blob.data_ptr(), src_off.data_ptr(), dst_blob.data_ptr(), dst_off.data_ptr(), ranges.data_ptr(),
+                                                           results.data_ptr(), totals.data_ptr(), n, dd, _stream_ptr()))
+    return results, totals
+
+
+def last_frames_range():
+    """zjni_last_frames_range (synchronises): {"served": buffers answered without an error, "frames": frames handed to the decoder, "edges": frames among them
+    decoded into scratch because the range cuts them, "errors": buffers that answered an error} of the last decompress_frames_range() on this device."""
+    import ctypes as C
+    out = (C.c_uint * 4)()
+    r = lib().zjni_last_frames_range(out)
+    if r != 0:
+        raise ZstdException(-r, "zjni_last_frames_range failed")
+    return dict(zip(("served", "frames", "edges", "errors"), [int(x) for x in out]))
+
+
 def stream_states(n, level, device="cuda"):
     """n compress-stream states of zjni_cstream_state_bytes(level) bytes each, zeroed: streams on which nothing has been done."""
     size = lib().zjni_cstream_state_bytes(level)

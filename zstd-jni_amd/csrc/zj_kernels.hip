@@ -32,6 +32,7 @@
 #include "zj_synth.h"
 #include "zj_frameinfo.h"
 #include "zj_frames.h"
+#include "zj_frames_range.h"
 
 #define ZJNI_ERR(code) ((size_t)0 - (size_t)(code))
 
@@ -3724,6 +3725,164 @@ int zjni_last_frames(unsigned* out4) {
     return 0;
 }
 
+// ---- ranged decompress (zj_frames_range.h) ----
+// per buffer: [rec n][q 5 x n][scan 5 x (n + 1)][totals 5].  The five quantities: entries of set A, entries of set B, compact source bytes of A, of B, scratch
+// bytes of the edge frames.
+// first walk, one lane per buffer like zj_frames_count_kernel: rules 1-4, the buffer's record and what the scans add up
+__global__ __launch_bounds__(64) void zj_range_count_kernel(const u8* __restrict__ src, const u64* __restrict__ off, const u64* __restrict__ dstOff, const u64* __restrict__ range,
+                                                            ZRRec* __restrict__ rec, u64* __restrict__ q, u64* __restrict__ total, u32 n) {
+    u64 const i = (u64)blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    u64 const lo = off[i], hi = off[i + 1], dlo = dstOff[i], dhi = dstOff[i + 1];
+    ZRRec r; u64 qq[5];
+    zj_range_count(src + lo, hi > lo ? hi - lo : 0, range[2 * i], range[2 * i + 1], dhi > dlo ? dhi - dlo : 0, r, qq);
+    rec[i] = r;
+    for (u32 k = 0; k < 5; k++) q[(u64)k * n + i] = qq[k];
+    if (total) total[i] = r.total;
+}
+// workgroup k: scan[k][0 .. n] = exclusive prefix sums of q[k][0 .. n), totals[k] = scan[k][n] (zj_pack_offsets_kernel's shape, five at once)
+__global__ __launch_bounds__(1024) void zj_range_scan_kernel(const u64* __restrict__ q, u64* __restrict__ scan, u64* __restrict__ totals, u32 n) {
+    __shared__ u64 part[1024];
+    u32 const t = threadIdx.x;
+    const u64* const in = q + (u64)blockIdx.x * n;
+    u64* const out = scan + (u64)blockIdx.x * ((u64)n + 1u);
+    u64 const per = ((u64)n + 1023u) / 1024u, lo0 = (u64)t * per, lo = lo0 < n ? lo0 : n, hi = lo + per < n ? lo + per : n;
+    u64 sum = 0;
+    for (u64 i = lo; i < hi; i++) sum += in[i];
+    part[t] = sum;
+    __syncthreads();
+    for (u32 d = 1; d < 1024u; d <<= 1) {
+        u64 const v = t >= d ? part[t - d] : 0;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    u64 run = t ? part[t - 1] : 0;
+    for (u64 i = lo; i < hi; i++) { out[i] = run; run += in[i]; }
+    if (t == 1023u) { out[n] = part[1023]; totals[blockIdx.x] = part[1023]; }
+}
+// second walk, one lane per buffer, from the recorded position of `first`: the entries of both sets and the copy runs; the lane of the last buffer closes the arrays.
+// Set B's sources lie behind set A's in the compact bytes (at scan[2][n]).
+__global__ __launch_bounds__(64) void zj_range_emit_kernel(const u8* __restrict__ src, const u64* __restrict__ off, const u64* __restrict__ dstOff, const ZRRec* __restrict__ rec,
+                                                           const u64* __restrict__ scan, u32 n, u64* __restrict__ srcA, u64* __restrict__ dstA, u64* __restrict__ srcB,
+                                                           u64* __restrict__ dstB, ZRCopy* __restrict__ in, ZRCopy* __restrict__ out) {
+    u64 const i = (u64)blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    u64 const n1 = (u64)n + 1u;
+    const u64* const fA = scan; const u64* const fB = scan + n1; const u64* const cA = scan + 2 * n1; const u64* const cB = scan + 3 * n1; const u64* const eB = scan + 4 * n1;
+    u64 const lo = off[i], hi = off[i + 1], a0 = fA[i], a1 = fA[i + 1], b0 = fB[i];
+    ZRRec const r = rec[i];
+    ZRCopy cin[3], cout[2];
+    zj_range_emit(src + lo, hi > lo ? hi - lo : 0, r, lo, dstOff[i], (u32)(a1 - a0 - 1u), cA[i], cA[n] + cB[i], eB[i], srcA + a0, dstA + a0, srcB + b0, dstB + b0, cin, cout);
+    in[i] = cin[0]; in[(u64)n + 2 * i] = cin[1]; in[(u64)n + 2 * i + 1] = cin[2];
+    out[2 * i] = cout[0]; out[2 * i + 1] = cout[1];
+    if (i + 1 == n) { srcA[a1] = cA[n]; dstA[a1] = dstA[a1 - 1]; srcB[fB[n]] = cA[n] + cB[n]; dstB[fB[n]] = eB[n]; }
+}
+// The bandwidth kernel: workgroup t moves what lies in tile t of the runs' key space.  keyIsDst: the key is the destination offset (source -> compact bytes),
+// otherwise the source offset (edge scratch -> the caller's slots).  16 aligned bytes per lane where both residues agree, else two 8-byte words; bytes at the ends.
+__global__ __launch_bounds__(256) void zj_range_gather_kernel(const ZRCopy* __restrict__ runs, u64 D, const u8* __restrict__ srcBase, u8* __restrict__ dstBase, u32 keyIsDst, u64 keyEnd) {
+    u64 const tLo = (u64)blockIdx.x * ZJ_RANGE_TILE, tHi = tLo + ZJ_RANGE_TILE < keyEnd ? tLo + ZJ_RANGE_TILE : keyEnd;
+    u32 const t = threadIdx.x;
+    for (u64 d = zj_range_tile_first(runs, D, tLo); d < D; d++) {
+        ZRCopy const c = runs[d];
+        if (c.key >= tHi) break;
+        u64 at = 0;
+        u64 const len = zj_range_tile_part(c, tLo, tHi, &at);
+        if (!len) continue;
+        const u8* const s = srcBase + (keyIsDst ? c.other : c.key) + at;
+        u8* const dd = dstBase + (keyIsDst ? c.key : c.other) + at;
+        ZRPlan const pl = zj_range_copy_plan((u64)(uintptr_t)s, (u64)(uintptr_t)dd, len);
+        if (t < pl.head) dd[t] = s[t];
+        const u8* const sb = s + pl.head; u8* const db = dd + pl.head;
+        if (pl.wide) for (u64 k = t; k < pl.body; k += 256) ((uint4*)db)[k] = ((const uint4*)sb)[k];
+        else for (u64 k = t; k < pl.body; k += 256) { u64 const a = ld64(sb + 16 * k), b = ld64(sb + 16 * k + 8); st64(db + 16 * k, a); st64(db + 16 * k + 8, b); }
+        if (t < pl.tail) db[(pl.body << 4) + t] = sb[(pl.body << 4) + t];
+    }
+}
+// One wave per buffer: the first error over its entries in frame order (edge first, interiors, edge last), the result, the stats (stat[4 .. 8)); a buffer with an
+// error gets its edge runs emptied, so the gather behind this kernel copies nothing for it.
+__global__ __launch_bounds__(64) void zj_range_finish_kernel(const ZRRec* __restrict__ rec, const u64* __restrict__ scan, const u64* __restrict__ resA, const u64* __restrict__ resB,
+                                                             u64* __restrict__ result, u32 n, ZRCopy* __restrict__ out, u32* stat) {
+    u32 const lane = threadIdx.x;
+    for (u32 i = blockIdx.x; i < n; i += gridDim.x) {
+        u32 const status = rec[i].status, e = rec[i].edges, frames = rec[i].frames;
+        if (status != ZJ_RANGE_SELECTED) {
+            if (lane == 0) { result[i] = status == ZJ_RANGE_NOTHING ? 0 : ZJ_ERR64(status); atomicAdd(&stat[status == ZJ_RANGE_NOTHING ? 4 : 7], 1u); }
+            continue;
+        }
+        u64 const a0 = scan[i], m = scan[i + 1] - a0 - 1u, b0 = scan[(u64)n + 1u + i];
+        u64 err = 0;
+        if (e & 1u) { u64 const v = resB[b0]; if (v > ((u64)1 << 40)) err = v; }
+        for (u64 base = 0; base < m && !err; base += 64) {
+            u64 const k = base + lane;
+            u64 const v = k < m ? resA[a0 + k] : 0;
+            unsigned long long const mask = __ballot(v > ((u64)1 << 40));
+            if (mask) err = __shfl(v, (int)(__ffsll((long long)mask) - 1), 64);
+        }
+        if (!err && (e & 2u)) { u64 const v = resB[b0 + (e & 1u)]; if (v > ((u64)1 << 40)) err = v; }
+        if (lane == 0) {
+            result[i] = err ? err : rec[i].hi - rec[i].lo;
+            if (err) { out[2 * (u64)i].len = 0; out[2 * (u64)i + 1].len = 0; }
+            atomicAdd(&stat[err ? 7 : 4], 1u); atomicAdd(&stat[5], frames); atomicAdd(&stat[6], zj_range_edge_count(e));
+        }
+    }
+}
+size_t zjni_decompress_frames_range_batch_device(const void* d_src, const uint64_t* d_src_off, void* d_dst, const uint64_t* d_dst_off, const uint64_t* d_range,
+                                                 uint64_t* d_result, uint64_t* d_total, size_t n, const zjni_ddict* ddict, void* stream) {
+    if (ddict && ddict->ordinal != t_dev && t_dev >= 0) return ZJNI_ERR(32);      // digested on another device
+    DevState* d = cur_state();
+    if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (n > 0xFFFFFFFFull) return ZJNI_ERR(72);
+    hipStream_t const st = (hipStream_t)stream;
+    BatchOrder order(d, stream);
+    if (!frames_state(d)) return ZJNI_ERR(64);
+    if (hipMemsetAsync(d->framesStat + 4, 0, 16, st) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (n == 0) return 0;
+    size_t const oRec = 0, oQ = zj_up16(n * sizeof(ZRRec)), oScan = oQ + zj_up16(5 * n * 8), oTot = oScan + zj_up16(5 * (n + 1) * 8), perBuf = oTot + 64;
+    size_t r = frames_room(d, perBuf, 0, st);
+    if (r != 0) return r;
+    u32 const gridN = (u32)((n + 63) / 64);
+    hipLaunchKernelGGL(zj_range_count_kernel, dim3(gridN), dim3(64), 0, st, (const u8*)d_src, (const u64*)d_src_off, (const u64*)d_dst_off, (const u64*)d_range,
+                       (ZRRec*)(d->framesBuf + oRec), (u64*)(d->framesBuf + oQ), (u64*)d_total, (u32)n);
+    hipLaunchKernelGGL(zj_range_scan_kernel, dim3(5), dim3(1024), 0, st, (const u64*)(d->framesBuf + oQ), (u64*)(d->framesBuf + oScan), (u64*)(d->framesBuf + oTot), (u32)n);
+    // the entry's only host wait: the five totals in one copy
+    if (hipMemcpyAsync((void*)d->framesE, d->framesBuf + oTot, 40, hipMemcpyDeviceToHost, st) != hipSuccess || hipEventRecord(d->evFramesE, st) != hipSuccess
+        || hipEventSynchronize(d->evFramesE) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    u64 const EA = d->framesE[0], EB = d->framesE[1], CA = d->framesE[2], CB = d->framesE[3], SB = d->framesE[4];
+    if (EA > 0xFFFFFFFFull) return ZJNI_ERR(72);
+    if (EA < n || EB > 2 * (u64)n) return ZJNI_ERR(ZJNI_ERROR_no_device);          // (every buffer has its closing entry and at most two edges)
+    // per entry and per run: [srcA EA + 1][dstA EA + 1][resA EA][srcB EB + 1][dstB EB + 1][resB EB][in 3n][out 2n][compact bytes CA + CB][edge scratch SB]
+    size_t const oSrcA = perBuf, oDstA = oSrcA + zj_up16((EA + 1) * 8), oResA = oDstA + zj_up16((EA + 1) * 8), oSrcB = oResA + zj_up16(EA * 8 + 8),
+                 oDstB = oSrcB + zj_up16((EB + 1) * 8), oResB = oDstB + zj_up16((EB + 1) * 8), oIn = oResB + zj_up16(EB * 8 + 8), oOut = oIn + zj_up16(3 * n * sizeof(ZRCopy)),
+                 oComp = oOut + zj_up16(2 * n * sizeof(ZRCopy)), oEdge = oComp + zj_up16(CA + CB) + 16, total = oEdge + zj_up16(SB) + 16;
+    if (CA + CB < CA || total < oComp || total < SB) return ZJNI_ERR(64);
+    if ((r = frames_room(d, total, perBuf, st)) != 0) return r;
+    u8* const fb = d->framesBuf;
+    ZRCopy* const in = (ZRCopy*)(fb + oIn); ZRCopy* const out = (ZRCopy*)(fb + oOut);
+    hipLaunchKernelGGL(zj_range_emit_kernel, dim3(gridN), dim3(64), 0, st, (const u8*)d_src, (const u64*)d_src_off, (const u64*)d_dst_off, (const ZRRec*)(fb + oRec),
+                       (const u64*)(fb + oScan), (u32)n, (u64*)(fb + oSrcA), (u64*)(fb + oDstA), (u64*)(fb + oSrcB), (u64*)(fb + oDstB), in, out);
+    u64 const tilesIn = (CA + CB + ZJ_RANGE_TILE - 1) / ZJ_RANGE_TILE, tilesOut = (SB + ZJ_RANGE_TILE - 1) / ZJ_RANGE_TILE;
+    if (tilesIn > 0x7FFFFFFFull || tilesOut > 0x7FFFFFFFull) return ZJNI_ERR(64);
+    if (tilesIn) hipLaunchKernelGGL(zj_range_gather_kernel, dim3((u32)tilesIn), dim3(256), 0, st, (const ZRCopy*)in, (u64)(3 * n), (const u8*)d_src, fb + oComp, 1u, CA + CB);
+    if (hipGetLastError() != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    // (a call with no interior frame has nothing but closing entries in set A: no launch)
+    if (EA > n && (r = decompress_chunked_ordered(fb + oComp, (const u64*)(fb + oSrcA), d_dst, (const u64*)(fb + oDstA), (u64*)(fb + oResA), (size_t)EA, ddict, stream)) != 0) return r;
+    if (EB && (r = decompress_chunked_ordered(fb + oComp, (const u64*)(fb + oSrcB), fb + oEdge, (const u64*)(fb + oDstB), (u64*)(fb + oResB), (size_t)EB, ddict, stream)) != 0) return r;
+    u32 const gridF = (u32)(n < (size_t)d->numCU * 8 ? n : (size_t)d->numCU * 8);
+    hipLaunchKernelGGL(zj_range_finish_kernel, dim3(gridF), dim3(64), 0, st, (const ZRRec*)(fb + oRec), (const u64*)(fb + oScan), (const u64*)(fb + oResA), (const u64*)(fb + oResB),
+                       (u64*)d_result, (u32)n, out, d->framesStat);
+    if (tilesOut) hipLaunchKernelGGL(zj_range_gather_kernel, dim3((u32)tilesOut), dim3(256), 0, st, (const ZRCopy*)out, (u64)(2 * n), (const u8*)(fb + oEdge), (u8*)d_dst, 0u, SB);
+    return hipGetLastError() == hipSuccess ? 0 : ZJNI_ERR(ZJNI_ERROR_no_device);
+}
+int zjni_last_frames_range(unsigned* out4) {
+    DevState* d = cur_state();
+    if (!d || !out4) return -(int)ZJNI_ERROR_no_device;
+    u32 h[4] = {0, 0, 0, 0};
+    if (hipDeviceSynchronize() != hipSuccess || (d->framesStat && hipMemcpy(h, d->framesStat + 4, sizeof h, hipMemcpyDeviceToHost) != hipSuccess)) return -(int)ZJNI_ERROR_no_device;
+    for (int k = 0; k < 4; k++) out4[k] = h[k];
+    return 0;
+}
+
 // ---- chunked compress ----
 size_t zjni_compressBound_chunked(size_t srcSize, size_t chunkSize) {
     if (chunkSize < 256 || chunkSize > ZJNI_BLOCKSIZE_MAX) return ZJNI_ERR(42);
@@ -3863,6 +4022,35 @@ size_t zjni_compress_chunked(void* dst, size_t dstCap, const void* src, size_t s
 }
 size_t zjni_decompress_frames(void* dst, size_t dstCap, const void* src, size_t srcSize) {
     return host_one_buffer(false, dst, dstCap, src, srcSize, 0, 0, 0);
+}
+
+// the ranged form: [srcOff 2][dstOff 2][result 1][range 2][total 1] fill the slot's first 64 bytes; the slot is as large as the range can get, not as the buffer
+size_t zjni_decompress_frames_range(void* dst, size_t dstCap, const void* src, size_t srcSize, unsigned long long lo, unsigned long long len, unsigned long long* total) {
+    DevState* d = cur_state();
+    if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if ((u64)dstCap > len) dstCap = (size_t)len;
+    if (srcSize > ((size_t)1 << 46) || dstCap > ((size_t)1 << 46)) return ZJNI_ERR(64);
+    if ((srcSize && !src) || (dstCap && !dst)) return ZJNI_ERR(72);
+    size_t const oSrc = 64, oDst = oSrc + zj_up16(srcSize), all = oDst + dstCap + 16;
+    SlotLock slotLock(d); StageSlot* const sl = slotLock.s;
+    if (!ensure_staging(sl, all)) return ZJNI_ERR(ZJNI_ERROR_unsupported);
+    hipStream_t const hst = sl->hostK;
+    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drainOnExit{hst};
+    u64* const h = (u64*)sl->hPinned;
+    h[0] = 0; h[1] = srcSize; h[2] = 0; h[3] = dstCap; h[4] = 0; h[5] = lo; h[6] = len; h[7] = 0;
+    if (srcSize) memcpy(sl->hPinned + oSrc, src, srcSize);
+    if (hipMemcpyAsync(sl->dStage, sl->hPinned, oSrc + srcSize, hipMemcpyHostToDevice, hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    u64* const dW = (u64*)sl->dStage;
+    size_t const r = zjni_decompress_frames_range_batch_device(sl->dStage + oSrc, dW, sl->dStage + oDst, dW + 2, dW + 5, dW + 4, dW + 7, 1, nullptr, hst);
+    if (zjni_isError(r)) return r;
+    if (hipMemcpyAsync(sl->hPinned + 32, sl->dStage + 32, 32, hipMemcpyDeviceToHost, hst) != hipSuccess || hipStreamSynchronize(hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    size_t const res = (size_t)h[4];
+    if (total) *total = h[7];
+    if (zjni_isError(res) || res == 0) return res;
+    if (res > dstCap) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (hipMemcpyAsync(sl->hPinned + oDst, sl->dStage + oDst, res, hipMemcpyDeviceToHost, hst) != hipSuccess || hipStreamSynchronize(hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    memcpy(dst, sl->hPinned + oDst, res);
+    return res;
 }
 
 }  // extern "C"
