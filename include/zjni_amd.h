@@ -366,6 +366,44 @@ size_t zjni_compress_batch_usingCDict(const void* const* src, const size_t* srcS
                                       size_t* result, size_t n, const zjni_cdict* cdict, int checksum);
 size_t zjni_compress_usingCDict(void* dst, size_t dstCapacity, const void* src, size_t srcSize, const zjni_cdict* cdict);
 
+/* ---- chunked compress with a dictionary, the caller's cuts and the frame sizes out (a record store: one segment = one buffer of one frame per record) ----
+ * zjni_compress_pieces_batch_device takes the layout, ordering, result convention, the one eight-byte-per-count read-back behind the counting kernel, the slicing
+ * under zjni_set_scratch_limit, n == 0 and the 72 for n or an entry count above 2^32 - 1 of zjni_compress_chunked_batch_device, and adds three things.
+ *  Cuts.  d_cut == NULL: the fixed grid, max(1, ceil(size / chunkSize)) pieces; with cdict, d_piece_first and d_piece_size NULL as well the call writes the bytes and
+ *    results of zjni_compress_chunked_batch_device(level, flags & 1, chunkSize).  d_cut given: buffer i's cuts are d_cut[d_cut_off[i] .. d_cut_off[i + 1]), in bytes
+ *    from the buffer's start, and its pieces exactly the gaps [0, c0), [c0, c1), ..., [c_last, size).  A list is legal when d_cut_off ascends at i, the cuts ascend
+ *    strictly, every cut lies in (0, size) and no piece exceeds chunkSize; an empty buffer with an empty list is the one frame of an empty input.  An illegal list
+ *    answers ZSTD_error_parameter_outOfBound (42) in d_result[i]: no byte of that slot is written, the buffer contributes ZERO entries to the index below, and the
+ *    other buffers of the call are not affected.  chunkSize (256 .. ZJNI_BLOCKSIZE_MAX, else the call returns 42) is then the largest piece allowed, and every piece
+ *    gets zjni_compressBound(chunkSize) of library scratch; pieces may be as small as one byte.
+ *  Dictionary.  Without cdict frame k is the frame zjni_compress_batch_device2 writes for the piece at `level` (0 means 3; a level not served: the call returns 42).
+ *    With cdict `level` is ignored and frame k is, byte for byte, the frame zjni_compress_batch_device_usingCDict writes for the piece with the same flag word into a
+ *    zjni_compressBound destination (attach and copy mode, negative levels); a piece that entry refuses answers its code, and the first such code is the buffer's
+ *    result.  A cdict digested on another device: what that entry answers (32).  flags: ZJNI_FRAME_CHECKSUM always, ZJNI_FRAME_NO_DICTID with a cdict;
+ *    ZJNI_FRAME_NO_CONTENTSIZE makes the call return 42 (frames without a content size can be neither split nor range-read afterwards).
+ *  Index.  d_piece_first[i] (when given, [n + 1]) = the entries before buffer i, d_piece_first[n] = E.  d_piece_size[e] (when given) = the compressed size of entry e:
+ *    for a buffer whose result is a size they sum to it, and frame e starts at d_dst_off[i] plus the sizes of the buffer's entries before e; for a buffer that
+ *    answered an error they are unspecified.  With d_piece_size given and E > pieceCap the call returns 70 before any compress work is queued; d_result is then
+ *    untouched.  A caller who keeps the index hands exactly the frames it wants to zjni_decompress_batch_device[_usingDDict]: no walk over the buffer.  The index is
+ *    the caller's memory: nothing about it is written into the stream.
+ * zjni_compressBound_pieces(srcSize, nPieces) = srcSize + (srcSize >> 8) + 64 * max(nPieces, 1), at least the sum of zjni_compressBound over any nPieces pieces of
+ * srcSize bytes: a slot of this size always fits.
+ * zjni_compress_pieces: the blocking form for ONE host buffer (cut == NULL: the fixed grid); pieceSize[0 .. min(E, pieceCap)) and *nPieces = E when given.
+ * zjni_decompress_frames_usingDDict / zjni_decompress_frames_range_usingDDict: zjni_decompress_frames / zjni_decompress_frames_range with a dictionary. */
+size_t zjni_compressBound_pieces(size_t srcSize, size_t nPieces);
+size_t zjni_compress_pieces_batch_device(const void* d_src, const uint64_t* d_src_off, void* d_dst, const uint64_t* d_dst_off,
+                                         uint64_t* d_result, size_t n, int level, int flags, size_t chunkSize,
+                                         const uint64_t* d_cut /* or NULL */, const uint64_t* d_cut_off /* [n + 1], with d_cut */,
+                                         const zjni_cdict* cdict /* or NULL */,
+                                         uint64_t* d_piece_first /* [n + 1] or NULL */, uint64_t* d_piece_size /* [pieceCap] or NULL */, size_t pieceCap,
+                                         void* stream);
+size_t zjni_compress_pieces(void* dst, size_t dstCapacity, const void* src, size_t srcSize, int level, int flags, size_t chunkSize,
+                            const uint64_t* cut, size_t nCut, const zjni_cdict* cdict,
+                            uint64_t* pieceSize /* or NULL */, size_t pieceCap, size_t* nPieces /* or NULL */);
+size_t zjni_decompress_frames_usingDDict(void* dst, size_t dstCapacity, const void* src, size_t srcSize, const zjni_ddict* ddict);
+size_t zjni_decompress_frames_range_usingDDict(void* dst, size_t dstCapacity, const void* src, size_t srcSize,
+                                               unsigned long long lo, unsigned long long len, unsigned long long* total /* or NULL */, const zjni_ddict* ddict);
+
 /* ---- hot path, host buffers (what a JNI batch native binds; stages through pinned memory) ---- */
 size_t zjni_decompress_batch(const void* const* src, const size_t* srcSize,
                              void* const* dst, const size_t* dstCapacity,

@@ -249,6 +249,17 @@ def lib():
         L.zjni_last_frames_range.argtypes = [C.POINTER(C.c_uint)]
         L.zjni_decompress_frames_range.restype = sz
         L.zjni_decompress_frames_range.argtypes = [vp, sz, vp, sz, C.c_ulonglong, C.c_ulonglong, C.POINTER(C.c_ulonglong)]
+    if hasattr(L, "zjni_compress_pieces_batch_device"):      # chunked compress with a dictionary, the caller's cuts, the frame sizes out
+        L.zjni_compressBound_pieces.restype = sz
+        L.zjni_compressBound_pieces.argtypes = [sz, sz]
+        L.zjni_compress_pieces_batch_device.restype = sz
+        L.zjni_compress_pieces_batch_device.argtypes = [vp, vp, vp, vp, vp, sz, C.c_int, C.c_int, sz, vp, vp, vp, vp, vp, sz, vp]
+        L.zjni_compress_pieces.restype = sz
+        L.zjni_compress_pieces.argtypes = [vp, sz, vp, sz, C.c_int, C.c_int, sz, vp, sz, vp, vp, sz, C.POINTER(sz)]
+        L.zjni_decompress_frames_usingDDict.restype = sz
+        L.zjni_decompress_frames_usingDDict.argtypes = [vp, sz, vp, sz, vp]
+        L.zjni_decompress_frames_range_usingDDict.restype = sz
+        L.zjni_decompress_frames_range_usingDDict.argtypes = [vp, sz, vp, sz, C.c_ulonglong, C.c_ulonglong, C.POINTER(C.c_ulonglong), vp]
     _lib = L
     return L
 
@@ -273,7 +284,9 @@ EXPORTS = ("zjni_version", "zjni_device_count", "zjni_init", "zjni_shutdown", "z
            "zjni_createCStream2", "zjni_cstream_pending",
            "zjni_decompress_frames_batch_device", "zjni_last_frames", "zjni_compressBound_chunked", "zjni_compress_chunked_batch_device",
            "zjni_compress_chunked", "zjni_decompress_frames",
-           "zjni_decompress_frames_range_batch_device", "zjni_last_frames_range", "zjni_decompress_frames_range")
+           "zjni_decompress_frames_range_batch_device", "zjni_last_frames_range", "zjni_decompress_frames_range",
+           "zjni_compressBound_pieces", "zjni_compress_pieces_batch_device", "zjni_compress_pieces",
+           "zjni_decompress_frames_usingDDict", "zjni_decompress_frames_range_usingDDict")
 
 
 # --------------------------------------------------------------------------- Java API mirror --

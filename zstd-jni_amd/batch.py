@@ -165,6 +165,61 @@ def compress_chunked(src_blob, src_off, dst_blob=None, dst_off=None, level=3, ch
     return dst_blob, dst_off, results
 
 
+def compress_bound_pieces(size, pieces):
+    """zjni_compressBound_pieces: size + (size >> 8) + 64 * max(pieces, 1) — a slot that fits any `pieces` pieces of a buffer of `size` bytes."""
+    return lib().zjni_compressBound_pieces(size, pieces)
+
+
+def compress_pieces(src_blob, src_off, dst_blob=None, dst_off=None, level=3, checksum=False, chunk=1 << 16, cuts=None, cut_off=None, dictionary=None, dict_id=True,
+                    sizes=False, piece_cap=None, results=None):
+    """Enqueue zjni_compress_pieces_batch_device on the current stream: compress_chunked() with three additions.  `cuts` / `cut_off` (int64 tensors; buffer i's cuts
+    are cuts[cut_off[i]:cut_off[i + 1]], bytes from its start) put the frame boundaries where the caller's records end instead of on the fixed grid; `chunk` is then
+    the largest piece allowed, and a buffer with an illegal list answers -42, writes nothing and owns no entry.  `dictionary` (a ZstdDictCompress; its level applies,
+    dict_id=False keeps its ID out of the headers) makes every frame the one compress(dictionary=...) writes for the piece.  sizes=True also returns the index:
+    piece_first int64[n + 1] (entries before buffer i; the last is E) and piece_size int64[E] (compressed size of every frame, in order), with which
+    decompress() reads single records without walking the buffer.  Returns (dst_blob, dst_off, results[, piece_first, piece_size]).  Without a dst_blob the slots
+    are compress_bound_pieces-sized (src_off and cut_off are read on the host for that: one wait).  `piece_cap`: the size of the piece_size tensor (default: the
+    number of pieces the lists describe); the call raises ZstdException(70) when E exceeds it."""
+    import torch
+    n = src_off.numel() - 1
+    dev = src_blob.device
+    if (cuts is None) != (cut_off is None):
+        raise ValueError("compress_pieces: cuts and cut_off go together")
+    src_sizes = counts = None
+    if dst_blob is None or (sizes and piece_cap is None):
+        src_sizes = (src_off[1:] - src_off[:-1]).clamp(min=0).cpu().tolist()
+        if cut_off is not None:
+            counts = [c + 1 for c in (cut_off[1:] - cut_off[:-1]).clamp(min=0).cpu().tolist()]
+        else:
+            counts = [max(1, -(-s // chunk)) for s in src_sizes]
+    if dst_blob is None:
+        offs = [0]
+        for s, c in zip(src_sizes, counts):
+            offs.append(offs[-1] + compress_bound_pieces(s, c))
+        dst_off = torch.tensor(offs, dtype=torch.int64, device=dev)
+        dst_blob = torch.empty(max(offs[-1], 1), dtype=torch.uint8, device=dev)[:offs[-1]]
+    elif dst_off is None:
+        raise ValueError("compress_pieces: a dst_blob needs its dst_off")
+    if results is None:
+        results = torch.empty(n, dtype=torch.int64, device=dev)
+    piece_first = piece_size = None
+    if sizes:
+        if piece_cap is None:
+            piece_cap = sum(counts)
+        piece_first = torch.empty(n + 1, dtype=torch.int64, device=dev)
+        piece_size = torch.empty(max(piece_cap, 1), dtype=torch.int64, device=dev)
+    if cuts is not None and cuts.numel() == 0:
+        cuts = torch.zeros(1, dtype=torch.int64, device=dev)          # (an empty tensor has no address, and no address means the fixed grid)
+    flags = (1 if checksum else 0) | (0 if dict_id else 4)
+    _check(lib().zjni_compress_pieces_batch_device(src_blob.data_ptr(), src_off.data_ptr(), dst_blob.data_ptr(), dst_off.data_ptr(), results.data_ptr(), n, level, flags, chunk,
+                                                   cuts.data_ptr() if cuts is not None else None, cut_off.data_ptr() if cut_off is not None else None,
+                                                   dictionary._ptr if dictionary is not None else None,
+                                                   piece_first.data_ptr() if sizes else None, piece_size.data_ptr() if sizes else None, piece_cap if sizes else 0, _stream_ptr()))
+    if sizes:
+        return dst_blob, dst_off, results, piece_first, piece_size[:int(piece_first[n].item())]
+    return dst_blob, dst_off, results
+
+
 def decompress_frames(src_blob, src_off, dst_blob, dst_off, results=None, dictionary=None):
     """Enqueue zjni_decompress_frames_batch_device on the current stream: decompress() for buffers of MANY concatenated frames (compress_chunked's output,
     pzstd, appended logs).  A buffer of at least two zstd frames that all record their content size is decoded one frame per wave slot instead of frame

@@ -77,3 +77,22 @@ ZJ_HD u64 zj_entry_owner(const u64* first, u64 n, u64 e) {
     while (hi - lo > 1) { u64 const mid = lo + (hi - lo) / 2; if (first[mid] <= e) lo = mid; else hi = mid; }
     return lo;
 }
+
+// ---- pieces: the caller's cuts (zjni_compress_pieces_batch_device) ----
+// A buffer of `size` bytes with the cuts cut[0 .. c): its pieces are the gaps [0, cut[0]), [cut[0], cut[1]), ..., [cut[c - 1], size).
+// zjni_compressBound_pieces: ZSTD_COMPRESSBOUND's small-input margin is at most (128 KiB >> 11) = 64 a piece, and the pieces' >> 8 terms sum to at most the whole's
+ZJ_HD u64 zj_pieces_bound(u64 size, u64 pieces) { return size + (size >> 8) + 64 * (pieces ? pieces : 1); }
+// a list without cuts: one piece, legal when it is not above `chunk` (an empty buffer is the one frame of an empty input)
+ZJ_HD bool zj_cut_none_ok(u64 size, u64 chunk) { return size <= chunk; }
+// cut k of c, one lane's share of the legality check: strictly above its left neighbour (0 for the first: no cut of 0), below `size`, the piece it closes not above
+// `chunk`; the last cut answers for the piece behind it as well
+ZJ_HD bool zj_cut_ok(const u64* cut, u64 c, u64 k, u64 size, u64 chunk) {
+    u64 const v = cut[k], left = k ? cut[k - 1] : 0;
+    if (v <= left || v >= size || v - left > chunk) return false;
+    return k + 1 < c || size - v <= chunk;
+}
+// where piece k begins in the source (the buffer begins at srcLo): behind cut k - 1, or on the fixed grid when the buffer has no list (cut == nullptr)
+ZJ_HD u64 zj_piece_src(u64 srcLo, u64 chunk, const u64* cut, u64 k) { return cut ? srcLo + (k ? cut[k - 1] : 0) : zj_chunk_src(srcLo, chunk, k); }
+// A buffer with an illegal list owns no entry of the caller's index, but its bytes lie between its neighbours' and an entry ends where the next one begins: inside
+// the call it is walked on the fixed grid (zj_chunk_count entries whose frames go nowhere), so that every entry of a legal buffer keeps its own extent.
+ZJ_HD u64 zj_pieces_walked(bool legal, u64 pieces, u64 size, u64 chunk) { return legal ? pieces : zj_chunk_count(size, chunk); }

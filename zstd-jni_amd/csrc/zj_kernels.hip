@@ -2910,6 +2910,9 @@ unsigned zjni_getDictID_fromCDict(const zjni_cdict* cd) { return cd ? cd->dictID
 // wave-per-frame entropy stage starting from the dictionary's tables.
 // Slices of 2 x ZJ_CHUNK_FRAMES: memset/classify/clear/match of slice s on the caller's stream, its entropy kernel on the side
 // stream — beside slice s+1's match kernel (which leaves most of every CU idle: one wave per SIMD, waiting on memory).
+// (the caller holds the device's BatchOrder; n in 1 .. 2^32 - 1, the CDict of this device)
+static size_t compress_cdict_ordered(DevState* d, const void* d_src, const uint64_t* d_src_off, void* d_dst, const uint64_t* d_dst_off,
+                                     uint64_t* d_result, size_t n, const zjni_cdict* cdict, u32 flags, void* stream);
 size_t zjni_compress_batch_device_usingCDict(const void* d_src, const uint64_t* d_src_off, void* d_dst, const uint64_t* d_dst_off,
                                              uint64_t* d_result, size_t n, const zjni_cdict* cdict, int checksum, void* stream) {
     if (!cdict) return ZJNI_ERR(32);
@@ -2919,8 +2922,11 @@ size_t zjni_compress_batch_device_usingCDict(const void* d_src, const uint64_t* 
     if (n == 0) return 0;
     if (n > 0xFFFFFFFFull) return ZJNI_ERR(72);
     BatchOrder order(d, stream);
+    return compress_cdict_ordered(d, d_src, d_src_off, d_dst, d_dst_off, d_result, n, cdict, zj_frame_flags(checksum), stream);
+}
+static size_t compress_cdict_ordered(DevState* d, const void* d_src, const uint64_t* d_src_off, void* d_dst, const uint64_t* d_dst_off,
+                                     uint64_t* d_result, size_t n, const zjni_cdict* cdict, u32 flags, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-    u32 const flags = zj_frame_flags(checksum);
     size_t chunk = 2 * ZJ_CHUNK_FRAMES;            // 2 048 match waves = every SIMD's second wave slot as well: more table requests in flight (measured: +15 % over 65 536)
     chunk = scratch_slice((size_t)ZC_TABLE_STRIDE + 2 * ((size_t)ZE_FRAME_STRIDE(ZC_MAX_SRC) + 12), chunk, 1);
     if (const char* ov = zj_tune("ZJNI_CD_SLICE")) { size_t const v = (size_t)atoll(ov); if (v >= 64) chunk = v; }
@@ -3990,8 +3996,120 @@ size_t zjni_compress_chunked_batch_device(const void* d_src, const uint64_t* d_s
     return hipGetLastError() == hipSuccess ? 0 : ZJNI_ERR(ZJNI_ERROR_no_device);
 }
 
+// ---- pieces: chunked compress with a dictionary, the caller's cuts and the frame sizes out ----
+size_t zjni_compressBound_pieces(size_t srcSize, size_t nPieces) { return (size_t)zj_pieces_bound(srcSize, nPieces); }
+// One wave per buffer: lanes stride the cut list, a wave-wide AND gives its legality.  idx[i] = the entries buffer i owns in the caller's index (0 for an illegal list),
+// cnt[i] = the entries it is walked as inside the call (zj_pieces_walked), ferr[i] = 0 or the 42 of an illegal list, which the place kernel's first-error rule then keeps.
+__global__ __launch_bounds__(64) void zj_pieces_count_kernel(const u64* __restrict__ off, u32 n, u64 chunk, const u64* __restrict__ cut, const u64* __restrict__ cutOff,
+                                                             u64* __restrict__ cnt, u64* __restrict__ idx, u64* __restrict__ ferr) {
+    u32 const lane = threadIdx.x;
+    for (u32 i = blockIdx.x; i < n; i += gridDim.x) {
+        u64 const lo = off[i], hi = off[i + 1], size = hi > lo ? hi - lo : 0;
+        bool ok = true; u64 pieces = zj_chunk_count(size, chunk);
+        if (cut) {                                                      // (uniform over the wave, as i and c are: every lane reaches the ballot)
+            u64 const c0 = cutOff[i], c1 = cutOff[i + 1], c = c1 > c0 ? c1 - c0 : 0;
+            ok = c1 >= c0 && (c || zj_cut_none_ok(size, chunk));
+            for (u64 k = lane; ok && k < c; k += 64) ok = zj_cut_ok(cut + c0, c, k, size, chunk);
+            ok = __ballot(!ok) == 0ull;
+            pieces = c + 1;
+        }
+        if (lane == 0) { cnt[i] = zj_pieces_walked(ok, pieces, size, chunk); idx[i] = ok ? pieces : 0; ferr[i] = ok ? 0 : ZJ_ERR64(42); }
+    }
+}
+// one lane per entry of the slice [a, a + m], its end included: where the piece begins in the source; its scratch destination is its place in the slice x bound
+__global__ __launch_bounds__(256) void zj_pieces_emit_kernel(const u64* __restrict__ off, const u64* __restrict__ first, const u64* __restrict__ idx, u32 n, u64 chunk, u64 bound,
+                                                             const u64* __restrict__ cut, const u64* __restrict__ cutOff, u64 a, u32 m, u64 E,
+                                                             u64* __restrict__ srcOffS, u64* __restrict__ dstOffS) {
+    u64 const j = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (j > m) return;
+    dstOffS[j] = j * bound;
+    u64 const e = a + j;
+    if (e >= E) { srcOffS[j] = off[n]; return; }
+    u64 const i = zj_entry_owner(first, n, e);
+    srcOffS[j] = zj_piece_src(off[i], chunk, (cut && idx[i]) ? cut + cutOff[i] : nullptr, e - first[i]);
+}
+// one lane per entry of the slice [a, a + m), behind its compress call: the entry's size goes to the caller's index; an entry of a buffer with an illegal list
+// answers that buffer's 42 instead of its frame's size, so the place kernel moves nothing of it
+__global__ __launch_bounds__(256) void zj_pieces_sizes_kernel(const u64* __restrict__ first, const u64* __restrict__ ifirst, const u64* __restrict__ idx, u32 n, u64 a, u32 m,
+                                                              u64* __restrict__ resS, u64* __restrict__ pieceSize, u64 pieceCap) {
+    u64 const j = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (j >= m) return;
+    u64 const e = a + j, i = zj_entry_owner(first, n, e);
+    if (!idx[i]) { resS[j] = ZJ_ERR64(42); return; }
+    u64 const p = ifirst[i] + (e - first[i]);
+    if (pieceSize && p < pieceCap) pieceSize[p] = resS[j];
+}
+size_t zjni_compress_pieces_batch_device(const void* d_src, const uint64_t* d_src_off, void* d_dst, const uint64_t* d_dst_off, uint64_t* d_result, size_t n,
+                                         int level, int flags, size_t chunkSize, const uint64_t* d_cut, const uint64_t* d_cut_off, const zjni_cdict* cdict,
+                                         uint64_t* d_piece_first, uint64_t* d_piece_size, size_t pieceCap, void* stream) {
+    if ((u32)flags & ZE_FLAG_NO_FCS) return ZJNI_ERR(42);          // a frame without a content size can be neither split nor range-read afterwards
+    if (!cdict) {
+        if (level == 0) level = 3;
+        if (!zj_level_served(level)) return ZJNI_ERR(42);
+    }
+    if (chunkSize < 256 || chunkSize > ZJNI_BLOCKSIZE_MAX) return ZJNI_ERR(42);
+    if (d_cut && !d_cut_off) return ZJNI_ERR(42);
+    if (cdict && cdict->ordinal != t_dev && t_dev >= 0) return ZJNI_ERR(32);      // digested on another device: zjni_compress_batch_device_usingCDict's answer
+    DevState* d = cur_state();
+    if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (n > 0xFFFFFFFFull) return ZJNI_ERR(72);
+    hipStream_t const st = (hipStream_t)stream;
+    if (n == 0) {
+        if (d_piece_first && hipMemsetAsync(d_piece_first, 0, 8, st) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+        return 0;
+    }
+    u32 const fl = cdict ? (zj_frame_flags(flags) & ~ZE_FLAG_NO_FCS) : (((u32)flags & 1u) ? ZE_FLAG_CHECKSUM : 0u);
+    BatchOrder order(d, stream);
+    if (!frames_state(d)) return ZJNI_ERR(64);
+    // per buffer: [cnt n][idx n][first n + 1][ifirst n + 1][carry n][ferr n]
+    size_t const nb = zj_up16((n + 1) * 8), oCnt = 0, oIdx = nb, oFirst = 2 * nb, oIfirst = 3 * nb, oCarry = 4 * nb, oFerr = 5 * nb, perBuf = 6 * nb;
+    size_t r = frames_room(d, perBuf, 0, st);
+    if (r != 0) return r;
+    u32 const gridN = (u32)((n + 255) / 256);
+    u32 const gridW = (u32)(n < (size_t)d->numCU * 8 ? n : (size_t)d->numCU * 8);
+    hipLaunchKernelGGL(zj_pieces_count_kernel, dim3(gridW), dim3(64), 0, st, (const u64*)d_src_off, (u32)n, (u64)chunkSize, (const u64*)d_cut, (const u64*)d_cut_off,
+                       (u64*)(d->framesBuf + oCnt), (u64*)(d->framesBuf + oIdx), (u64*)(d->framesBuf + oFerr));
+    hipLaunchKernelGGL(zj_pack_offsets_kernel, dim3(1), dim3(1024), 0, st, (const u64*)(d->framesBuf + oCnt), (u64*)(d->framesBuf + oFirst), (u32)n);
+    hipLaunchKernelGGL(zj_pack_offsets_kernel, dim3(1), dim3(1024), 0, st, (const u64*)(d->framesBuf + oIdx), (u64*)(d->framesBuf + oIfirst), (u32)n);
+    if (hipMemsetAsync(d->framesBuf + oCarry, 0, nb, st) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    // the one host wait: E (the entries walked) and, eight bytes beside it, the entries of the caller's index — they differ by the walks of illegal lists
+    u64 E = 0, EI = 0;
+    if (hipMemcpyAsync((void*)(d->framesE + 1), (const u64*)(d->framesBuf + oIfirst) + n, 8, hipMemcpyDeviceToHost, st) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if ((r = frames_read_total(d, (const u64*)(d->framesBuf + oFirst) + n, st, &E)) != 0) return r;
+    EI = d->framesE[1];
+    if (E > 0xFFFFFFFFull || EI > 0xFFFFFFFFull) return ZJNI_ERR(72);
+    if (E < n || EI > E) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (d_piece_size && EI > pieceCap) return ZJNI_ERR(70);
+    if (d_piece_first && hipMemcpyAsync(d_piece_first, d->framesBuf + oIfirst, (n + 1) * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    // per slice of S entries: [srcOffS S + 1][dstOffS S + 1][resS S][packSize S][packDst S][scratch destinations: S x zjni_compressBound(chunk)]
+    size_t const bound = (size_t)zj_compress_bound(chunkSize);
+    size_t S = scratch_slice(bound + 48, ZJ_CHUNK_FRAMES, 4);
+    if (S > E) S = (size_t)E;
+    size_t const ns = zj_up16((S + 1) * 8), oSrcS = perBuf, oDstS = oSrcS + ns, oResS = oDstS + ns, oPSize = oResS + ns, oPDst = oPSize + ns, oOut = oPDst + ns;
+    size_t const total = oOut + zj_up16(S * bound) + 16;
+    if ((r = frames_room(d, total, perBuf, st)) != 0) return r;
+    u8* const fb = d->framesBuf;
+    for (u64 a = 0; a < E; a += S) {
+        u32 const m = (u32)(E - a < S ? E - a : S);
+        hipLaunchKernelGGL(zj_pieces_emit_kernel, dim3(m / 256 + 1), dim3(256), 0, st, (const u64*)d_src_off, (const u64*)(fb + oFirst), (const u64*)(fb + oIdx), (u32)n, (u64)chunkSize,
+                           (u64)bound, (const u64*)d_cut, (const u64*)d_cut_off, a, m, E, (u64*)(fb + oSrcS), (u64*)(fb + oDstS));
+        if (hipGetLastError() != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+        r = cdict ? compress_cdict_ordered(d, d_src, (const u64*)(fb + oSrcS), fb + oOut, (const u64*)(fb + oDstS), (u64*)(fb + oResS), m, cdict, fl, stream)
+                  : compress_chunked_ordered(d_src, (const u64*)(fb + oSrcS), fb + oOut, (const u64*)(fb + oDstS), (u64*)(fb + oResS), m, level, fl, stream);
+        if (r != 0) return r;
+        hipLaunchKernelGGL(zj_pieces_sizes_kernel, dim3((m + 255) / 256), dim3(256), 0, st, (const u64*)(fb + oFirst), (const u64*)(fb + oIfirst), (const u64*)(fb + oIdx), (u32)n, a, m,
+                           (u64*)(fb + oResS), (u64*)d_piece_size, (u64)pieceCap);
+        hipLaunchKernelGGL(zj_chunks_place_kernel, dim3(gridW), dim3(64), 0, st, (const u64*)(fb + oFirst), (const u64*)d_dst_off, (u32)n, a, m, (const u64*)(fb + oResS),
+                           (u64*)(fb + oCarry), (u64*)(fb + oFerr), (u64*)(fb + oPSize), (u64*)(fb + oPDst));
+        u32 const gridP = (u32)(m < (u32)d->numCU * 8u ? m : (u32)d->numCU * 8u);
+        hipLaunchKernelGGL(zj_pack_kernel, dim3(gridP), dim3(256), 0, st, (const u8*)(fb + oOut), (const u64*)(fb + oDstS), (const u64*)(fb + oPSize), (u8*)d_dst, (const u64*)(fb + oPDst), m);
+    }
+    hipLaunchKernelGGL(zj_chunks_verdict_kernel, dim3(gridN), dim3(256), 0, st, (const u64*)d_dst_off, (u32)n, (const u64*)(fb + oCarry), (const u64*)(fb + oFerr), (u64*)d_result);
+    return hipGetLastError() == hipSuccess ? 0 : ZJNI_ERR(ZJNI_ERROR_no_device);
+}
+
 // ---- blocking forms for one host buffer, staged like zjni_compress2 / zjni_decompress: [srcOff 2][dstOff 2][result 1][pad][src][dst] in one staging slot ----
-static size_t host_one_buffer(bool compress, void* dst, size_t dstCap, const void* src, size_t srcSize, int level, int checksum, size_t chunkSize) {
+static size_t host_one_buffer(bool compress, void* dst, size_t dstCap, const void* src, size_t srcSize, int level, int checksum, size_t chunkSize, const zjni_ddict* ddict = nullptr) {
     DevState* d = cur_state();
     if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
     if (srcSize > ((size_t)1 << 46) || dstCap > ((size_t)1 << 46)) return ZJNI_ERR(64);
@@ -4007,7 +4125,7 @@ static size_t host_one_buffer(bool compress, void* dst, size_t dstCap, const voi
     if (hipMemcpyAsync(sl->dStage, sl->hPinned, oSrc + srcSize, hipMemcpyHostToDevice, hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
     const u64* const dOff = (const u64*)sl->dStage;
     size_t const r = compress ? zjni_compress_chunked_batch_device(sl->dStage + oSrc, dOff, sl->dStage + oDst, dOff + 2, (u64*)sl->dStage + 4, 1, level, checksum, chunkSize, hst)
-                              : zjni_decompress_frames_batch_device(sl->dStage + oSrc, dOff, sl->dStage + oDst, dOff + 2, (u64*)sl->dStage + 4, 1, nullptr, hst);
+                              : zjni_decompress_frames_batch_device(sl->dStage + oSrc, dOff, sl->dStage + oDst, dOff + 2, (u64*)sl->dStage + 4, 1, ddict, hst);
     if (zjni_isError(r)) return r;
     if (hipMemcpyAsync(sl->hPinned + 32, sl->dStage + 32, 8, hipMemcpyDeviceToHost, hst) != hipSuccess || hipStreamSynchronize(hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
     size_t const res = (size_t)h[4];
@@ -4023,9 +4141,55 @@ size_t zjni_compress_chunked(void* dst, size_t dstCap, const void* src, size_t s
 size_t zjni_decompress_frames(void* dst, size_t dstCap, const void* src, size_t srcSize) {
     return host_one_buffer(false, dst, dstCap, src, srcSize, 0, 0, 0);
 }
+size_t zjni_decompress_frames_usingDDict(void* dst, size_t dstCap, const void* src, size_t srcSize, const zjni_ddict* ddict) {
+    return host_one_buffer(false, dst, dstCap, src, srcSize, 0, 0, 0, ddict);
+}
+// zjni_compress_pieces_batch_device for one host buffer: [srcOff 2][dstOff 2][result 1][cutOff 2][pad][pieceFirst 2][pad] fill the slot's first 128 bytes, then
+// [src][cuts][piece sizes][dst]
+size_t zjni_compress_pieces(void* dst, size_t dstCap, const void* src, size_t srcSize, int level, int flags, size_t chunkSize, const uint64_t* cut, size_t nCut,
+                            const zjni_cdict* cdict, uint64_t* pieceSize, size_t pieceCap, size_t* nPieces) {
+    DevState* d = cur_state();
+    if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (srcSize > ((size_t)1 << 46) || dstCap > ((size_t)1 << 46) || nCut > ((size_t)1 << 32) || pieceCap > ((size_t)1 << 32)) return ZJNI_ERR(64);
+    if ((srcSize && !src) || (dstCap && !dst)) return ZJNI_ERR(72);
+    if (!cut) nCut = 0;
+    if (!pieceSize) pieceCap = 0;
+    size_t const oSrc = 128, oCut = oSrc + zj_up16(srcSize), oPs = oCut + zj_up16(nCut * 8), oDst = oPs + zj_up16(pieceCap * 8), total = oDst + dstCap + 16;
+    SlotLock slotLock(d); StageSlot* const sl = slotLock.s;
+    if (!ensure_staging(sl, total)) return ZJNI_ERR(ZJNI_ERROR_unsupported);
+    hipStream_t const hst = sl->hostK;
+    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drainOnExit{hst};
+    u64* const h = (u64*)sl->hPinned;
+    memset(h, 0, 128);
+    h[1] = srcSize; h[3] = dstCap; h[6] = nCut;
+    if (srcSize) memcpy(sl->hPinned + oSrc, src, srcSize);
+    if (nCut) memcpy(sl->hPinned + oCut, cut, nCut * 8);
+    if (hipMemcpyAsync(sl->dStage, sl->hPinned, oPs, hipMemcpyHostToDevice, hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    u64* const dW = (u64*)sl->dStage;
+    size_t const r = zjni_compress_pieces_batch_device(sl->dStage + oSrc, dW, sl->dStage + oDst, dW + 2, dW + 4, 1, level, flags, chunkSize,
+                                                       cut ? (const u64*)(sl->dStage + oCut) : nullptr, cut ? dW + 5 : nullptr, cdict,
+                                                       dW + 8, pieceSize ? (u64*)(sl->dStage + oPs) : nullptr, pieceCap, hst);
+    if (zjni_isError(r)) return r;
+    if (hipMemcpyAsync(sl->hPinned + 32, sl->dStage + 32, 8, hipMemcpyDeviceToHost, hst) != hipSuccess
+        || hipMemcpyAsync(sl->hPinned + 64, sl->dStage + 64, 16, hipMemcpyDeviceToHost, hst) != hipSuccess || hipStreamSynchronize(hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    size_t const res = (size_t)h[4], E = (size_t)h[9];
+    if (nPieces) *nPieces = E;
+    if (zjni_isError(res)) return res;
+    if (res > dstCap || (pieceSize && E > pieceCap)) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (res && hipMemcpyAsync(sl->hPinned + oDst, sl->dStage + oDst, res, hipMemcpyDeviceToHost, hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (pieceSize && E && hipMemcpyAsync(sl->hPinned + oPs, sl->dStage + oPs, E * 8, hipMemcpyDeviceToHost, hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (hipStreamSynchronize(hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (res) memcpy(dst, sl->hPinned + oDst, res);
+    if (pieceSize && E) memcpy(pieceSize, sl->hPinned + oPs, E * 8);
+    return res;
+}
 
 // the ranged form: [srcOff 2][dstOff 2][result 1][range 2][total 1] fill the slot's first 64 bytes; the slot is as large as the range can get, not as the buffer
 size_t zjni_decompress_frames_range(void* dst, size_t dstCap, const void* src, size_t srcSize, unsigned long long lo, unsigned long long len, unsigned long long* total) {
+    return zjni_decompress_frames_range_usingDDict(dst, dstCap, src, srcSize, lo, len, total, nullptr);
+}
+size_t zjni_decompress_frames_range_usingDDict(void* dst, size_t dstCap, const void* src, size_t srcSize, unsigned long long lo, unsigned long long len, unsigned long long* total,
+                                               const zjni_ddict* ddict) {
     DevState* d = cur_state();
     if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
     if ((u64)dstCap > len) dstCap = (size_t)len;
@@ -4041,7 +4205,7 @@ size_t zjni_decompress_frames_range(void* dst, size_t dstCap, const void* src, s
     if (srcSize) memcpy(sl->hPinned + oSrc, src, srcSize);
     if (hipMemcpyAsync(sl->dStage, sl->hPinned, oSrc + srcSize, hipMemcpyHostToDevice, hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
     u64* const dW = (u64*)sl->dStage;
-    size_t const r = zjni_decompress_frames_range_batch_device(sl->dStage + oSrc, dW, sl->dStage + oDst, dW + 2, dW + 5, dW + 4, dW + 7, 1, nullptr, hst);
+    size_t const r = zjni_decompress_frames_range_batch_device(sl->dStage + oSrc, dW, sl->dStage + oDst, dW + 2, dW + 5, dW + 4, dW + 7, 1, ddict, hst);
     if (zjni_isError(r)) return r;
     if (hipMemcpyAsync(sl->hPinned + 32, sl->dStage + 32, 32, hipMemcpyDeviceToHost, hst) != hipSuccess || hipStreamSynchronize(hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
     size_t const res = (size_t)h[4];
