@@ -538,6 +538,14 @@ int zjni_last_decode_lists(unsigned* out4);
 /* zjni_last_decode_lists plus out5[4]: frames that are a header and ONE stored (raw or RLE) block — what ZSTD_compress2 writes for data that does not compress
  * (N/compress/zstd_compress.c:4591-4692, ZSTD_noCompressBlock) — which stage 1 of the large-batch pipeline copies itself; they are on none of the three lists. */
 int zjni_last_decode_lists2(unsigned* out5);
+/* TEST ENTRY, not on any data path: the entropy stage (zj_encode_kernel, mode 0) on sequences the CALLER wrote instead of a match finder's.  n sources on the device
+ * (offsets as everywhere), each ONE block of at most 128 KiB; HOST arrays: h_rec = {ll, ml, offBase, pos} per sequence (pos: where its literals start; the sequences
+ * tile the source in order), frame i's at h_rec[4 * h_rec_off[i] .. 4 * h_rec_off[i + 1]), h_meta[3 i ..] = {nbSeq, litSize, lastLL}.  Records that do not tile their
+ * source answer an error (42) before anything is launched.  stagedLds: 0 = the dynamic LDS of the entropy launches without a dictionary (the stage alone), 1 = that of
+ * the dictionary pipeline's (frames of at most 4096 bytes are staged in LDS).  grid > 0: at most that many workgroups (1: one workgroup meets every frame in turn).
+ * One launch for the frames to 64 KiB, one for the wider ones.  d_result[i] as zjni_compress_batch_device2.  Synchronous. */
+size_t zjni_test_compress_records_batch_device(const void* d_src, const uint64_t* d_src_off, const uint32_t* h_rec, const uint64_t* h_rec_off, const uint32_t* h_meta,
+                                               void* d_dst, const uint64_t* d_dst_off, uint64_t* d_result, size_t n, int level, int checksum, int stagedLds, int grid, void* stream);
 /* Name of the kernel a route's match-finder time (zjni_last_timing out[0]) belongs to. */
 const char* zjni_route_kernel(int route);
 /* The source revision the library was built from ("unknown" when the build had no git): profiles and PMC passes are stamped with it. */

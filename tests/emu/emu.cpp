@@ -360,6 +360,66 @@ extern "C" unsigned long long emu_compress_chain(const unsigned char* src, unsig
     return r;
 }
 
+// The entropy stage on records the CALLER wrote (tests/seqrecords.py): rec[4 i ..] = {ll, ml, offBase, pos} of sequence i, litSize and lastLL as a match finder
+// would report them — a one-block frame through ze_compress with `pre`, in a frame slot laid out as the match kernels leave it (records, then the literal
+// offsets; the common stride to 64 KiB, the wide one above).  level = level | frame flags << 8 (as emu_compress_split) | 0x800: the launch's dynamic LDS holds
+// the entropy stage only (sizeof(ZEEntropy): frames <= ZE_SMALL_MAX are NOT staged in LDS — the product's entropy launches without a dictionary).
+extern "C" unsigned long long emu_compress_records(const unsigned char* src, unsigned srcSize, const unsigned* rec, unsigned nbSeq, unsigned litSize, unsigned lastLL,
+                                                   unsigned char* dst, unsigned dstCap, unsigned level) {
+    EMU_IO(src, srcSize, dst, dstCap);
+    if (srcSize > ZE_BLOCK_MAX) return ZJ_ERR64(201);
+    Grp<1> g;
+    u32 const flags = (level >> 8) & ZE_FLAG_MASK, ldsBytes = (level & 0x800u) ? (u32)sizeof(ZEEntropy) : 160u * 1024u; level &= 0xFFu;
+    u32 const maxSrc = srcSize <= 65536u ? 65536u : ZE_WIDE_MAX_SRC;
+    if (nbSeq > ZE_FRAME_MAXSEQ(maxSrc)) return ZJ_ERR64(201);
+    EmuWg& wg = emu_wg(); ZEncShared* sh = wg.sh; u8* lds = wg.lds; u8* ws = wg.ws;
+    u8* fs = (u8*)malloc(ZE_FRAME_STRIDE(maxSrc)); memset(fs, 0xC3, ZE_FRAME_STRIDE(maxSrc));
+    ZESeq* const seqs = (ZESeq*)fs; u32* const litOff = (u32*)(fs + (size_t)ZE_FRAME_MAXSEQ(maxSrc) * 16u);
+    u32 lit = 0;
+    for (u32 i = 0; i < nbSeq; i++) { ZESeq s; s.ll = rec[4 * i]; s.ml = rec[4 * i + 1]; s.off = rec[4 * i + 2]; s.pos = rec[4 * i + 3]; seqs[i] = s; litOff[i] = lit; lit += s.ll; }
+    u32 meta[3] = { nbSeq, litSize, lastLL };
+    ZEPre pre; pre.seqs = seqs; pre.litOff = litOff; pre.meta = meta;
+    ZjProf pf; pf.start(nullptr);
+    u64 const r = ze_compress(g, *sh, lds, src, srcSize, dst, dstCap, level, ws, pf, &pre, flags, nullptr, ldsBytes);
+    free(fs);
+    return r;
+}
+
+// A frame of several CALLER-CUT blocks (each at most 128 KiB, the frame of any size) on the caller's records: the entropy role of the pipelined kernel itself —
+// ze_pipe_entropy_init writes the header and resets the state carried between blocks, ze_pipe_entropy_step runs ze_compress_t(pre, ba) on the block the "parse wave"
+// published (here: the caller) and carries sh.dictHufRep / the previous tables on.  blk[4 b ..] = {size, nbSeq, litSize, lastLL} of block b, rec = the records of all
+// blocks in order, pos relative to the block.  That role always writes the header of frames above 128 KiB (a 4-byte content size): for a smaller frame the
+// caller compares from the first block header on.  level = level | frame flags << 8.
+extern "C" unsigned long long emu_compress_records_blocks(const unsigned char* src, unsigned srcSize, const unsigned* rec, const unsigned* blk, unsigned nBlocks,
+                                                          unsigned char* dst, unsigned dstCap, unsigned level) {
+    EMU_IO(src, srcSize, dst, dstCap);
+    Grp<1> g;
+    u32 const flags = (level >> 8) & ZE_FLAG_MASK; level &= 0xFFu;
+    {   u64 total = 0;
+        for (u32 b = 0; b < nBlocks; b++) { if (blk[4 * b] > ZE_BLOCK_MAX || blk[4 * b] == 0 || blk[4 * b + 1] > ZE_MAX_SEQ) return ZJ_ERR64(201); total += blk[4 * b]; }
+        if (total != srcSize || nBlocks == 0) return ZJ_ERR64(201); }
+    EmuWg& wg = emu_wg(); ZEncShared* sh = wg.sh; u8* lds = wg.lds; u8* ws0 = wg.ws;
+    static u8* ws1 = nullptr;
+    if (!ws1) { ws1 = (u8*)malloc(ZE_SCRATCH_BYTES); memset(ws1, 0x3C, ZE_SCRATCH_BYTES); }
+    ZEPipe pipe; memset(&pipe, 0xA5, sizeof pipe); pipe.ready = 0; pipe.done = 0; pipe.err = 0;
+    ZEPipeE st; ZjProf pf; pf.start(nullptr);
+    ze_pipe_entropy_init(g, *sh, st, dst, dstCap, srcSize, level, flags);
+    u32 at = 0; const unsigned* r = rec;
+    for (u32 b = 0; b < nBlocks && !st.finished; b++) {
+        u32 const size = blk[4 * b], nb = blk[4 * b + 1];
+        u8* const ws = (b & 1u) ? ws1 : ws0;
+        ZESeq* const seqs = (ZESeq*)(ws + ZE_WS_SEQ); u32* const litOff = (u32*)(ws + ZE_WS_BODY);
+        u32 lit = 0;
+        for (u32 i = 0; i < nb; i++, r += 4) { ZESeq s; s.ll = r[0]; s.ml = r[1]; s.off = r[2]; s.pos = r[3]; seqs[i] = s; litOff[i] = lit; lit += s.ll; }
+        ZEPipeBlk k; k.start = at; k.size = size; k.nbSeq = nb; k.litSize = blk[4 * b + 2]; k.lastLL = blk[4 * b + 3]; k.isFirst = b == 0u ? 1u : 0u;
+        k.lastBlock = b + 1u == nBlocks ? 1u : 0u; k.assumePrev = 0u; k.prevU = 0u;
+        pipe.blk[b & 1u] = k; pipe.ready = b + 1u;
+        ze_pipe_entropy_step(g, *sh, lds, pipe, st, src, srcSize, dst, dstCap, level, flags, ws0, ws1, pf, 160u * 1024u);
+        at += size;
+    }
+    return st.result;
+}
+
 // dictionary compression: digest (ZSTD_createCDict) + ZSTD_CCtx_refCDict / ZSTD_compress2
 #include "../../zstd-jni_amd/csrc/zj_cdict.h"
 extern "C" void* emu_cdict_create(const unsigned char* dict, unsigned dictSize, unsigned level) {

@@ -66,16 +66,27 @@ def _literals(rnd, n, kind):
     return raw if kind == "raw" else raw.translate(_TEXT)
 
 
-def build(blocks, level=3, checksum=False, window_log=0, dictionary=None, literals="text", seed=1):
+def build(blocks, level=3, checksum=False, window_log=0, dictionary=None, literals="text", seed=1, ext_rep=True):
     """blocks = [([(ll, ml, offset), ...], trailing literals), ...] -> (frame, content, shape).  The content is what the triples
     mean: ll literal bytes, then ml bytes each equal to the byte `offset` positions back (copied in runs of at most `offset`
     bytes, which is the same as byte by byte), the dictionary's content in front.  literals: "text" eight letters (Huffman),
-    "raw" random bytes, "rle" one value."""
+    "raw" random bytes, "rle" one value; a bytes object: the frame's literal bytes themselves, taken run after run (tests/seqrecords.py
+    chooses histograms with it).  ext_rep=False: searchForExternalRepcodes off — every offset is stored as offset + 3, no repcode is written."""
     from oracle import ref
     assert level <= 9                                  # from level 16 on the library may re-split blocks
     L = _lib()
     d = as_dict(dictionary)
     rnd = random.Random(seed)
+    if isinstance(literals, (bytes, bytearray)):
+        given, taken = bytes(literals), [0]
+
+        def lits(n):
+            taken[0] += n
+            assert taken[0] <= len(given), "more literals asked for than given"
+            return given[taken[0] - n:taken[0]]
+    else:
+        def lits(n):
+            return _literals(rnd, n, literals)
     out = bytearray(d.content if d else b"")
     base = len(out)
     n_seq = sum(len(s) for s, _ in blocks) + len(blocks)
@@ -83,7 +94,7 @@ def build(blocks, level=3, checksum=False, window_log=0, dictionary=None, litera
     i = 0
     for seqs, tail in blocks:
         for ll, ml, off in seqs:
-            out += _literals(rnd, ll, literals)
+            out += lits(ll)
             assert ml >= 3 and 1 <= off <= len(out), (ll, ml, off, len(out))
             arr[i].offset, arr[i].litLength, arr[i].matchLength = off, ll, ml
             i += 1
@@ -92,7 +103,7 @@ def build(blocks, level=3, checksum=False, window_log=0, dictionary=None, litera
                 s = len(out) - off
                 out += out[s:s + n]
                 ml -= n
-        out += _literals(rnd, tail, literals)
+        out += lits(tail)
         arr[i].offset, arr[i].litLength, arr[i].matchLength = 0, tail, 0       # the block delimiter
         i += 1
     content = bytes(out[base:])
@@ -100,7 +111,7 @@ def build(blocks, level=3, checksum=False, window_log=0, dictionary=None, litera
     try:
         params = [(100, level), (201, int(checksum)), (105, 3),                  # compressionLevel, checksumFlag, minMatch
                   (1008, 1), (1009, 1),                                          # blockDelimiters: explicit; validateSequences
-                  (1016, 1)]                                                     # searchForExternalRepcodes: on (below level 10 "auto" means off: no repcode would be written)
+                  (1016, 1 if ext_rep else 2)]                                   # searchForExternalRepcodes: on (below level 10 "auto" means off: no repcode would be written); 2 = off
         if window_log:
             params.append((101, window_log))
         for p, v in params:
@@ -124,8 +135,9 @@ def walk(frame):
     fhd = frame[4]
     single, didc, fcs = (fhd >> 5) & 1, fhd & 3, fhd >> 6
     pos = 5 + (0 if single else 1) + (0, 1, 2, 4)[didc] + (single if fcs == 0 else 1 << fcs)
-    blocks = []
+    blocks, first = [], pos
     while True:
+        assert pos + 3 <= len(frame), "the frame ends inside its blocks"
         bh = int.from_bytes(frame[pos:pos + 3], "little")
         last, typ, size = bh & 1, (bh >> 1) & 3, bh >> 3
         pos += 3
@@ -158,7 +170,7 @@ def walk(frame):
         pos = rec["end"]
         if last:
             break
-    return {"blocks": blocks, "checksum": bool(fhd & 4), "size": pos + (4 if fhd & 4 else 0), "dict_id": didc != 0}
+    return {"blocks": blocks, "checksum": bool(fhd & 4), "size": pos + (4 if fhd & 4 else 0), "dict_id": didc != 0, "header": first}
 
 
 def simple(shape):

@@ -260,6 +260,9 @@ def lib():
         L.zjni_decompress_frames_usingDDict.argtypes = [vp, sz, vp, sz, vp]
         L.zjni_decompress_frames_range_usingDDict.restype = sz
         L.zjni_decompress_frames_range_usingDDict.argtypes = [vp, sz, vp, sz, C.c_ulonglong, C.c_ulonglong, C.POINTER(C.c_ulonglong), vp]
+    if hasattr(L, "zjni_test_compress_records_batch_device"):      # test entry: the entropy stage on the caller's records
+        L.zjni_test_compress_records_batch_device.restype = sz
+        L.zjni_test_compress_records_batch_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, sz, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     _lib = L
     return L
 
@@ -286,7 +289,8 @@ EXPORTS = ("zjni_version", "zjni_device_count", "zjni_init", "zjni_shutdown", "z
            "zjni_compress_chunked", "zjni_decompress_frames",
            "zjni_decompress_frames_range_batch_device", "zjni_last_frames_range", "zjni_decompress_frames_range",
            "zjni_compressBound_pieces", "zjni_compress_pieces_batch_device", "zjni_compress_pieces",
-           "zjni_decompress_frames_usingDDict", "zjni_decompress_frames_range_usingDDict")
+           "zjni_decompress_frames_usingDDict", "zjni_decompress_frames_range_usingDDict",
+           "zjni_test_compress_records_batch_device")
 
 
 # --------------------------------------------------------------------------- Java API mirror --

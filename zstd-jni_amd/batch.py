@@ -335,6 +335,43 @@ def pack(results, dst_blob, dst_off, out=None, out_off=None):
     return out, out_off
 
 
+def _test_compress_records(datas, records, level, checksum=False, staged_lds=False, grid=0):
+    """TEST ENTRY (zjni_test_compress_records_batch_device): the entropy stage on sequences the caller wrote.  datas: the sources (bytes, one block each);
+    records[i] = (flat [ll, ml, offBase, pos] * nbSeq, litSize, lastLL) for source i.  staged_lds: the dynamic LDS of the dictionary pipeline's entropy launch
+    (frames to 4 KiB staged in LDS) instead of the plain one; grid: at most that many workgroups.  Returns a list of frames (bytes) or negative error codes."""
+    import ctypes as C
+    n = len(datas)
+    for data, (rec, _, _) in zip(datas, records):                      # what the entry itself does not refuse: sizes the level's frames never have, offsets that reach in front of the source
+        if len(data) > (131072 if level <= 4 else 16384):
+            raise ValueError("_test_compress_records: levels 5 to 8 serve frames to 16 KiB, the others to 128 KiB")
+        for q in range(0, len(rec), 4):
+            if rec[q + 2] > rec[q + 3] + rec[q] + 3:
+                raise ValueError("_test_compress_records: an offset beyond the start of the source")
+    offs, rec_off, flat, meta = [0], [0], [], []
+    for data, (rec, lit_size, last_ll) in zip(datas, records):
+        offs.append(offs[-1] + len(data))
+        rec_off.append(rec_off[-1] + len(rec) // 4)
+        flat += rec
+        meta += [len(rec) // 4, lit_size, last_ll]
+    dev = "cuda"
+    src = torch.frombuffer(bytearray(b"".join(datas) or b"\0"), dtype=torch.uint8).to(dev)
+    src_off = torch.tensor(offs, dtype=torch.int64, device=dev)
+    caps = [0]
+    for data in datas:
+        caps.append(caps[-1] + lib().zjni_compressBound(len(data)) + 64)
+    dst = torch.zeros(caps[-1], dtype=torch.uint8, device=dev)
+    dst_off = torch.tensor(caps, dtype=torch.int64, device=dev)
+    results = torch.zeros(max(n, 1), dtype=torch.int64, device=dev)
+    h_rec = (C.c_uint32 * max(len(flat), 1))(*flat)
+    h_off = (C.c_uint64 * (n + 1))(*rec_off)
+    h_meta = (C.c_uint32 * max(len(meta), 1))(*meta)
+    _check(lib().zjni_test_compress_records_batch_device(src.data_ptr(), src_off.data_ptr(), C.addressof(h_rec), C.addressof(h_off), C.addressof(h_meta), dst.data_ptr(),
+                                                         dst_off.data_ptr(), results.data_ptr(), n, level, 1 if checksum else 0, 1 if staged_lds else 0, grid, _stream_ptr()))
+    res = results.cpu().tolist()
+    out = dst.cpu().numpy().tobytes()
+    return [out[caps[i]:caps[i] + res[i]] if res[i] >= 0 else res[i] for i in range(n)]
+
+
 def last_timing():
     """ms of the stages of the last large-batch device calls (HIP events on the launch stream, see zjni_last_timing2):
     {"match": .., "dec_prep": .., "dec_seq": .., "dec_exec": .., "dec_fused": .., "match_wide": ..}; -1 where a stage did not run."""

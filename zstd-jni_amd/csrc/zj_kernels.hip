@@ -2597,6 +2597,80 @@ size_t zjni_compress_batch_device2(const void* d_src, const uint64_t* d_src_off,
     if (!zj_level_served(level)) return ZJNI_ERR(42);
     return compress_chunked(d_src, d_src_off, d_dst, d_dst_off, d_result, n, level, checksum ? ZE_FLAG_CHECKSUM : 0u, stream);
 }
+// Test entry (include/zjni_amd.h, "introspection for tests/bench"): zj_encode_kernel in mode 0 on records the CALLER wrote, so that tests reach the wave64 code of the
+// entropy stage with quantities no match finder emits on request.  Host code only: the frame slots ([records][literal offsets], as the match kernels leave them) are
+// laid out on the host and copied into a buffer of this call's own; one launch for the frames to 64 KiB (the common stride), one for the wider ones, as the product's
+// two entropy launches.  Synchronous, and nothing of it stays allocated.
+size_t zjni_test_compress_records_batch_device(const void* d_src, const uint64_t* d_src_off, const uint32_t* h_rec, const uint64_t* h_rec_off, const uint32_t* h_meta,
+                                               void* d_dst, const uint64_t* d_dst_off, uint64_t* d_result, size_t n, int level, int checksum, int stagedLds, int grid, void* stream) {
+    DevState* d = cur_state();
+    if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (level < 1 || level > ZJ_LEVEL_MAX || !h_rec_off || !h_meta || (!h_rec && n && h_rec_off[n])) return ZJNI_ERR(42);
+    if (n == 0) return 0;
+    if (n > 65536) return ZJNI_ERR(72);
+    hipStream_t st = (hipStream_t)stream;
+    std::vector<u64> so(n + 1);
+    if (hipMemcpyAsync(so.data(), d_src_off, (n + 1) * 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    std::vector<u32> lists[2];                                   // [0] frames to 64 KiB, [1] wider ones
+    u32 const maxSrcOf[2] = { 65536u, (u32)ZE_WIDE_MAX_SRC };
+    for (size_t i = 0; i < n; i++) {
+        u64 const size = so[i + 1] - so[i]; u32 const w = size > 65536u ? 1u : 0u;
+        u64 const nb = h_rec_off[i + 1] - h_rec_off[i];
+        if (so[i + 1] < so[i] || size > ZE_BLOCK_MAX || h_rec_off[i + 1] < h_rec_off[i] || nb != h_meta[3 * i] || nb > ZE_FRAME_MAXSEQ(maxSrcOf[w])) return ZJNI_ERR(42);
+        // the kernel trusts its records (a match finder wrote them): nothing that reads or writes outside the frame may reach it
+        u64 lit = 0, at = 0;
+        for (u64 q = 0; q < nb; q++) {
+            const u32* const s = h_rec + 4 * (h_rec_off[i] + q);                       // ll, ml, offBase, pos
+            if (s[3] != at || s[1] < 3u || s[2] < 1u || (u64)s[3] + s[0] + s[1] > size) return ZJNI_ERR(42);
+            lit += s[0]; at += (u64)s[0] + s[1];
+        }
+        if (at + h_meta[3 * i + 2] != size || lit + h_meta[3 * i + 2] != h_meta[3 * i + 1]) return ZJNI_ERR(42);
+        lists[w].push_back((u32)i);
+    }
+    size_t off[2][3], total = 64;                                // per list: frame slots, meta, list; 64 bytes of counters in front ([0] |A|, [1] |B|, [2] work A, [3] work B)
+    for (int w = 0; w < 2; w++) {
+        size_t const m = lists[w].size();
+        off[w][0] = total; total += m * (size_t)ZE_FRAME_STRIDE(maxSrcOf[w]);
+        off[w][1] = total; total += (m * 12 + 63) & ~(size_t)63;
+        off[w][2] = total; total += (m * 4 + 63) & ~(size_t)63;
+    }
+    std::vector<u8> image(total, (u8)0xC3);                       // (what no record covers is poisoned, as a slot a previous call used would be)
+    {   u32* const c = (u32*)image.data(); memset(c, 0, 64); c[0] = (u32)lists[0].size(); c[1] = (u32)lists[1].size(); }
+    for (int w = 0; w < 2; w++) {
+        for (size_t k = 0; k < lists[w].size(); k++) {
+            u32 const i = lists[w][k]; u32 const nb = h_meta[3 * (size_t)i];
+            u8* const fs = image.data() + off[w][0] + k * (size_t)ZE_FRAME_STRIDE(maxSrcOf[w]);
+            memcpy(fs, h_rec + 4 * h_rec_off[i], (size_t)nb * 16);
+            u32* const litOff = (u32*)(fs + (size_t)ZE_FRAME_MAXSEQ(maxSrcOf[w]) * 16u); u32 lit = 0;
+            for (u32 q = 0; q < nb; q++) { litOff[q] = lit; lit += h_rec[4 * (h_rec_off[i] + q)]; }
+            memcpy(image.data() + off[w][1] + k * 12, h_meta + 3 * (size_t)i, 12);
+            ((u32*)(image.data() + off[w][2]))[k] = i;
+        }
+    }
+    BatchOrder order(d, stream);
+    u8* buf = nullptr;
+    if (hipMalloc(&buf, total) != hipSuccess) { (void)hipGetLastError(); return ZJNI_ERR(64); }
+    size_t r = 0;
+    if (hipMemcpyAsync(buf, image.data(), total, hipMemcpyHostToDevice, st) != hipSuccess) r = ZJNI_ERR(ZJNI_ERROR_no_device);
+    u32 const levelWord = (u32)zj_level3_word(level), flags = checksum ? ZE_FLAG_CHECKSUM : 0u;
+    // the dynamic LDS of the product's entropy launches: the stage alone (no dictionary: nothing is staged), or with room for a frame of ZE_SMALL_MAX bytes (the dictionary pipeline's launch)
+    u32 const ldsRun = stagedLds ? (u32)ZE_SMALL_LDS_BYTES : (u32)sizeof(ZEEntropy);
+    size_t gridMax = (size_t)(stagedLds ? d->encGridSmall : d->encGridLvl[1]);
+    if (gridMax > (size_t)d->encGrid) gridMax = (size_t)d->encGrid;                 // a scratch slot per workgroup
+    if (grid > 0 && (size_t)grid < gridMax) gridMax = (size_t)grid;
+    for (int w = 0; w < 2 && r == 0; w++) {
+        size_t const m = lists[w].size();
+        if (!m) continue;
+        u32* const ctr = (u32*)buf;
+        hipLaunchKernelGGL(zj_encode_kernel, dim3((u32)(m < gridMax ? m : gridMax)), dim3(64), ldsRun, st, (const u8*)d_src, (const u64*)d_src_off, (u8*)d_dst,
+                           (const u64*)d_dst_off, (u64*)d_result, levelWord, (const u32*)(buf + off[w][2]), (const u32*)(ctr + w), ctr + 2 + w, d->encScratch, (unsigned long long*)nullptr,
+                           buf + off[w][0], maxSrcOf[w], (const u32*)(buf + off[w][1]), 0u, (const u32*)nullptr, (u32*)nullptr, flags, (const ZECDictDev*)nullptr, ldsRun, 0u, 0xFFFFFFFFu);
+        if (hipGetLastError() != hipSuccess) r = ZJNI_ERR(ZJNI_ERROR_no_device);
+    }
+    if (hipStreamSynchronize(st) != hipSuccess && r == 0) r = ZJNI_ERR(ZJNI_ERROR_no_device);
+    (void)hipFree(buf);
+    return r;
+}
 // Stream frames (include/zjni_amd.h): n streams, each buffered whole, through zj_encode_stream_kernel.
 size_t zjni_compress_stream_batch_device(const void* d_src, const uint64_t* d_src_off, void* d_dst, const uint64_t* d_dst_off, uint64_t* d_result, size_t n, int level, int checksum,
                                          const uint32_t* d_flush_at, const uint64_t* d_flush_off, const uint32_t* d_mode, void* stream) {
