@@ -404,6 +404,71 @@ size_t zjni_decompress_frames_usingDDict(void* dst, size_t dstCapacity, const vo
 size_t zjni_decompress_frames_range_usingDDict(void* dst, size_t dstCapacity, const void* src, size_t srcSize,
                                                unsigned long long lo, unsigned long long len, unsigned long long* total /* or NULL */, const zjni_ddict* ddict);
 
+/* ---- indexed range reads: many byte ranges per call by a caller-held index, no walk over the frame headers ----
+ * The ranged entry above walks every frame header of every buffer for any range and answers one range per buffer.  A caller who knows the sizes of its frames
+ * (zjni_compress_pieces_batch_device returns them) prepares an index once and reads by it: R requests per call, any number per buffer, found by bisection.
+ *
+ * THE INDEX of n buffers and E entries lives in the caller's device memory, zjni_index_bytes(n, E) bytes (a multiple of 256), all values uint64, in this order:
+ *     first[n + 1]   entries before each buffer; first[n] = E
+ *     valid[n]       0, or the error code (2 .. 2^32 - 1) that answers every request for the buffer
+ *     C[E + 1]       exclusive running sums of the entries' compressed sizes over the whole batch (C[0] = 0)
+ *     U[E + 1]       exclusive running sums of the entries' content sizes over the whole batch (U[0] = 0)
+ * An entry is a whole number of frames, usually one; a coarser index (several frames an entry) is legal, the decoder reads such a slice as it reads any buffer.
+ * Callers may store the index and may write one themselves.
+ * zjni_index_from_sizes_device builds it from d_piece_first[n + 1], d_piece_size[E] and d_piece_content[E] for any buffers of concatenated frames.  Buffer i is
+ * illegal, valid[i] = ZSTD_error_parameter_outOfBound (42), when d_piece_first does not ascend at i, when d_piece_first[i + 1] exceeds E, or when one of its sizes
+ * or content sizes exceeds 2^32 - 1 (such a value counts 0 in the sums); the other buffers are not affected.  The sums are one parallel scan over E.
+ * zjni_index_from_pieces_device writes the same index from what a zjni_compress_pieces_batch_device call took (the UNCOMPRESSED d_src_off, chunkSize, d_cut,
+ * d_cut_off) and gave (d_result, d_piece_first, d_piece_size; E = d_piece_first[n]): content sizes come from the cuts, or from the fixed grid when d_cut is NULL,
+ * and a buffer whose d_result is an error carries that code in valid.  Both builders are asynchronous on `stream`, wait for nothing on the host, and take n == 0
+ * and E == 0; n or E above 2^32 - 1: 72.
+ *
+ * zjni_decompress_index_range_batch_device: d_src / d_src_off[n + 1] are the n buffers of frames, d_req[3R] = (b_r, lo_r, len_r) asks for decoded bytes
+ * [lo, lo + len) of buffer b, and request r's slot is d_dst + d_dst_off[r] .. d_dst_off[r + 1] (ascending with r).  Requests are independent: any number per
+ * buffer, in any buffer order, overlapping or not; a frame two requests select is decoded twice.  A request is decided in this order, the first rule that applies
+ * answers for it.
+ *  1. Index.  b >= n answers 42; valid[b] != 0 answers that code (a value outside 2 .. 2^32 - 1, or first[b] .. first[b + 1] not inside 0 .. E: 42); a source extent
+ *     d_src_off[b + 1] - d_src_off[b] (0 when not ascending) other than C[first[b + 1]] - C[first[b]] answers ZSTD_error_srcSize_wrong (72).  d_total[r] = ~0 - 1.
+ *  2. Range clamp.  T = U[first[b + 1]] - U[first[b]]; d_total[r] = T; lo' = min(lo, T), hi' = min(lo + len, T) with a saturating sum.  lo' == hi': the result
+ *     is 0, nothing is decoded or written.
+ *  3. Slot.  A slot below hi' - lo' answers 70; nothing is decoded or written.
+ *  4. Selection, by bisection over U: `first` is the entry holding decoded byte lo', `last` the one holding byte hi' - 1 (an entry without content holds no byte);
+ *     every entry from first to last is decoded, entries without content between them included, AND NO OTHER ENTRY IS LOOKED AT: neither its header nor its bytes
+ *     are read.  Edge and interior entries, the scratch of an edge and ZJNI_RANGE_EDGE_MAX (64 above it) are rule 4 of the ranged entry above.
+ *  5. Answer.  hi' - lo', with exactly the bytes [lo', hi') of the buffer's decoded content in the slot and no other byte of d_dst written.  When selected entries
+ *     answer errors the result is the code of the lowest-numbered such entry, as in the ranged entry, where an entry's answer is what
+ *     zjni_decompress_batch_device_usingDDict gives for its bytes alone with a capacity of exactly the content size the index states; an entry that decodes WITHOUT
+ *     error to another size than the index states answers ZSTD_error_corruption_detected (20) (an entry that holds more than the index states does not fit its
+ *     slot and answers the decoder's 70).  Bytes inside the first hi' - lo' bytes of the slot are then unspecified, and nothing outside them is written.
+ * The index is the caller's memory and may hold anything.  Whatever it holds, no byte outside buffer b's source extent is read for request r and no byte outside
+ * request r's slot or the library's scratch is written: every derived offset is clamped, and a request whose selected entries' sums do not ascend inside the
+ * selection answers 20: its interior entries are handed to the decoder with slots of no byte, so none of them is written anywhere.  What a false index answers otherwise is wrong data or an entry's error, as a false header would.
+ * Asynchronous on `stream` except for one read-back of 40 bytes behind the request kernel and its scans (entry counts and scratch sizes: the pipelines size their
+ * launches on the host), as in the ranged entry.  Scratch as there (zjni_set_scratch_limit: 64 above it).  R == 0, n == 0 and E == 0 are legal; n, E, R or an entry
+ * count above 2^32 - 1: 72; a ddict digested on another device: 32.  d_total may be NULL.
+ * zjni_last_index_range (synchronises; diagnostics) of the last indexed call on this device: out4[0] requests served (rules 2-5 reached without an error), out4[1]
+ * entries handed to the decoder, out4[2] edge entries among them, out4[3] requests that answered an error.
+ * zjni_decompress_index_range: the blocking form for ONE host buffer with its nPieces sizes and content sizes in host memory.  It selects on the host by the same
+ * rules and sends ONLY the selected entries' compressed bytes and their slice of the index across the link; answer, bytes and *total (may be NULL) are those of
+ * staging the whole buffer. */
+size_t zjni_index_bytes(size_t n, size_t E);
+size_t zjni_index_from_sizes_device(size_t n, const uint64_t* d_piece_first /* [n + 1] */, const uint64_t* d_piece_size /* [E] */,
+                                    const uint64_t* d_piece_content /* [E] */, size_t E, void* d_index, void* stream);
+size_t zjni_index_from_pieces_device(const uint64_t* d_src_off /* [n + 1], of the uncompressed buffers */, size_t n, size_t chunkSize,
+                                     const uint64_t* d_cut /* or NULL */, const uint64_t* d_cut_off /* [n + 1], with d_cut */,
+                                     const uint64_t* d_result /* [n] or NULL */, const uint64_t* d_piece_first /* [n + 1] */, const uint64_t* d_piece_size /* [E] */,
+                                     size_t E, void* d_index, void* stream);
+size_t zjni_decompress_index_range_batch_device(const void* d_src, const uint64_t* d_src_off /* [n + 1] */, size_t n, const void* d_index, size_t E,
+                                                const uint64_t* d_req /* [3R]: b_r, lo_r, len_r */,
+                                                void* d_dst, const uint64_t* d_dst_off /* [R + 1] */,
+                                                uint64_t* d_result /* [R] */, uint64_t* d_total /* [R] or NULL */, size_t R,
+                                                const zjni_ddict* ddict /* may be NULL */, void* stream);
+int zjni_last_index_range(unsigned out4[4]);
+size_t zjni_decompress_index_range(void* dst, size_t dstCapacity, const void* src, size_t srcSize,
+                                   unsigned long long lo, unsigned long long len,
+                                   const uint64_t* pieceSize, const uint64_t* pieceContent, size_t nPieces,
+                                   unsigned long long* total /* or NULL */, const zjni_ddict* ddict /* may be NULL */);
+
 /* ---- hot path, host buffers (what a JNI batch native binds; stages through pinned memory) ---- */
 size_t zjni_decompress_batch(const void* const* src, const size_t* srcSize,
                              void* const* dst, const size_t* dstCapacity,

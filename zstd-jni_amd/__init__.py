@@ -260,6 +260,19 @@ def lib():
         L.zjni_decompress_frames_usingDDict.argtypes = [vp, sz, vp, sz, vp]
         L.zjni_decompress_frames_range_usingDDict.restype = sz
         L.zjni_decompress_frames_range_usingDDict.argtypes = [vp, sz, vp, sz, C.c_ulonglong, C.c_ulonglong, C.POINTER(C.c_ulonglong), vp]
+    if hasattr(L, "zjni_decompress_index_range_batch_device"):      # range reads by a caller-held index
+        L.zjni_index_bytes.restype = sz
+        L.zjni_index_bytes.argtypes = [sz, sz]
+        L.zjni_index_from_sizes_device.restype = sz
+        L.zjni_index_from_sizes_device.argtypes = [sz, vp, vp, vp, sz, vp, vp]
+        L.zjni_index_from_pieces_device.restype = sz
+        L.zjni_index_from_pieces_device.argtypes = [vp, sz, sz, vp, vp, vp, vp, vp, sz, vp, vp]
+        L.zjni_decompress_index_range_batch_device.restype = sz
+        L.zjni_decompress_index_range_batch_device.argtypes = [vp, vp, sz, vp, sz, vp, vp, vp, vp, vp, sz, vp, vp]
+        L.zjni_last_index_range.restype = C.c_int
+        L.zjni_last_index_range.argtypes = [C.POINTER(C.c_uint)]
+        L.zjni_decompress_index_range.restype = sz
+        L.zjni_decompress_index_range.argtypes = [vp, sz, vp, sz, C.c_ulonglong, C.c_ulonglong, vp, vp, sz, C.POINTER(C.c_ulonglong), vp]
     if hasattr(L, "zjni_test_compress_records_batch_device"):      # test entry: the entropy stage on the caller's records
         L.zjni_test_compress_records_batch_device.restype = sz
         L.zjni_test_compress_records_batch_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, sz, C.c_int, C.c_int, C.c_int, C.c_int, vp]
@@ -290,7 +303,29 @@ EXPORTS = ("zjni_version", "zjni_device_count", "zjni_init", "zjni_shutdown", "z
            "zjni_decompress_frames_range_batch_device", "zjni_last_frames_range", "zjni_decompress_frames_range",
            "zjni_compressBound_pieces", "zjni_compress_pieces_batch_device", "zjni_compress_pieces",
            "zjni_decompress_frames_usingDDict", "zjni_decompress_frames_range_usingDDict",
+           "zjni_index_bytes", "zjni_index_from_sizes_device", "zjni_index_from_pieces_device", "zjni_decompress_index_range_batch_device",
+           "zjni_last_index_range", "zjni_decompress_index_range",
            "zjni_test_compress_records_batch_device")
+
+
+def decompress_index_range(src, lo, length, piece_size, piece_content, dictionary=None, capacity=None):
+    """zjni_decompress_index_range: decoded bytes [lo, lo + length) of ONE host buffer of concatenated frames whose entries' compressed sizes and content sizes
+    the caller holds (sequences of ints).  Only the selected entries' bytes cross the link.  Returns (bytes, total): the range clamped to the buffer's content,
+    and the buffer's whole decoded size.  `capacity`: the destination's size (default: as much as the range can take)."""
+    n = len(piece_size)
+    if len(piece_content) != n:
+        raise ValueError("decompress_index_range: piece_size and piece_content go together")
+    sizes, contents = (C.c_uint64 * max(n, 1))(*piece_size), (C.c_uint64 * max(n, 1))(*piece_content)
+    if capacity is None:
+        capacity = max(0, min(length, sum(contents[:n]) - min(lo, sum(contents[:n]))))
+    dst = C.create_string_buffer(max(capacity, 1))
+    total = C.c_ulonglong(0)
+    buf = bytes(src)
+    r = lib().zjni_decompress_index_range(dst, capacity, buf, len(buf), lo, length, sizes, contents, n, C.byref(total),
+                                          dictionary._ptr if dictionary is not None else None)
+    if lib().zjni_isError(r):
+        raise ZstdException(r)
+    return dst.raw[:r], total.value
 
 
 # --------------------------------------------------------------------------- Java API mirror --

@@ -276,6 +276,79 @@ def last_frames_range():
     return dict(zip(("served", "frames", "edges", "errors"), [int(x) for x in out]))
 
 
+def index_bytes(n, entries):
+    """zjni_index_bytes: the bytes of a prepared index for n buffers and `entries` entries (first[n + 1], valid[n], C[entries + 1], U[entries + 1], all uint64)."""
+    return lib().zjni_index_bytes(n, entries)
+
+
+def _index_tensor(n, entries, device):
+    return torch.empty(max(index_bytes(n, entries) // 8, 1), dtype=torch.int64, device=device)
+
+
+def index_from_sizes(piece_first, piece_size, piece_content, index=None):
+    """Enqueue zjni_index_from_sizes_device on the current stream: the prepared index (an int64 tensor; see index_bytes) of n buffers of concatenated frames from
+    piece_first int64[n + 1], piece_size int64[E] and piece_content int64[E].  A buffer at which piece_first does not ascend or exceeds E, or with a size above
+    2^32 - 1, carries 42 in the index and every read of it answers -42.  No host wait."""
+    n, entries = piece_first.numel() - 1, piece_size.numel()
+    if piece_content.numel() != entries:
+        raise ValueError("index_from_sizes: piece_size and piece_content go together")
+    if index is None:
+        index = _index_tensor(n, entries, piece_first.device)
+    _check(lib().zjni_index_from_sizes_device(n, piece_first.data_ptr(), piece_size.data_ptr() if entries else None, piece_content.data_ptr() if entries else None,
+                                              entries, index.data_ptr(), _stream_ptr()))
+    return index
+
+
+def index_from_pieces(src_off, results, piece_first, piece_size, chunk=1 << 16, cuts=None, cut_off=None, index=None):
+    """Enqueue zjni_index_from_pieces_device on the current stream: the prepared index of what compress_pieces(sizes=True) returned, from what that call took — the
+    UNCOMPRESSED src_off, chunk, cuts / cut_off — and gave: results, piece_first, piece_size.  Content sizes come from the cuts (or the fixed grid); a buffer whose
+    result is an error carries that code.  No host wait."""
+    n, entries = src_off.numel() - 1, piece_size.numel()
+    if (cuts is None) != (cut_off is None):
+        raise ValueError("index_from_pieces: cuts and cut_off go together")
+    if index is None:
+        index = _index_tensor(n, entries, src_off.device)
+    if cuts is not None and cuts.numel() == 0:
+        cuts = torch.zeros(1, dtype=torch.int64, device=src_off.device)
+    _check(lib().zjni_index_from_pieces_device(src_off.data_ptr(), n, chunk, cuts.data_ptr() if cuts is not None else None, cut_off.data_ptr() if cut_off is not None else None,
+                                               results.data_ptr() if results is not None else None, piece_first.data_ptr(), piece_size.data_ptr() if entries else None,
+                                               entries, index.data_ptr(), _stream_ptr()))
+    return index
+
+
+def decompress_index_range(src_blob, src_off, index, entries, requests, dst_blob, dst_off, results=None, totals=None, dictionary=None):
+    """Enqueue zjni_decompress_index_range_batch_device on the current stream: `requests` is an int64[R, 3] (or [3R]) tensor of (buffer, lo, len); request r leaves
+    the decoded bytes [lo, lo + len) of that buffer, clamped to its content, at dst_off[r].  The frames are found by bisection in `index` (index_from_sizes /
+    index_from_pieces; `entries` = its E): no frame header outside the selection is read, and any number of requests may name one buffer.  Returns (results
+    int64[R], totals int64[R]) as decompress_frames_range does.  The library waits once per call for the entry counts.  last_index_range() says how the call went."""
+    n = src_off.numel() - 1
+    if requests.dtype != torch.int64 or not requests.is_contiguous() or requests.numel() % 3:
+        raise ValueError("decompress_index_range: requests must be a contiguous int64 tensor of (buffer, lo, len) triples")
+    count = requests.numel() // 3
+    if dst_off.numel() != count + 1:
+        raise ValueError("decompress_index_range: dst_off needs one slot per request")
+    if results is None:
+        results = torch.empty(count, dtype=torch.int64, device=src_blob.device)
+    if totals is None:
+        totals = torch.empty(count, dtype=torch.int64, device=src_blob.device)
+    dd = dictionary._ptr if dictionary is not None else None
+    _check(lib().zjni_decompress_index_range_batch_device(src_blob.data_ptr(), src_off.data_ptr(), n, index.data_ptr(), entries, requests.data_ptr() if count else None,
+                                                          dst_blob.data_ptr(), dst_off.data_ptr(), results.data_ptr() if count else None,
+                                                          totals.data_ptr() if count else None, count, dd, _stream_ptr()))
+    return results, totals
+
+
+def last_index_range():
+    """zjni_last_index_range (synchronises): {"served": requests answered without an error, "entries": index entries handed to the decoder, "edges": entries among
+    them decoded into scratch because the range cuts them, "errors": requests that answered an error} of the last decompress_index_range() on this device."""
+    import ctypes as C
+    out = (C.c_uint * 4)()
+    r = lib().zjni_last_index_range(out)
+    if r != 0:
+        raise ZstdException(-r, "zjni_last_index_range failed")
+    return dict(zip(("served", "entries", "edges", "errors"), [int(x) for x in out]))
+
+
 def stream_states(n, level, device="cuda"):
     """n compress-stream states of zjni_cstream_state_bytes(level) bytes each, zeroed: streams on which nothing has been done."""
     size = lib().zjni_cstream_state_bytes(level)

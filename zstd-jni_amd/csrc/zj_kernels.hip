@@ -33,6 +33,7 @@
 #include "zj_frameinfo.h"
 #include "zj_frames.h"
 #include "zj_frames_range.h"
+#include "zj_index.h"
 
 #define ZJNI_ERR(code) ((size_t)0 - (size_t)(code))
 
@@ -3963,6 +3964,243 @@ int zjni_last_frames_range(unsigned* out4) {
     return 0;
 }
 
+// ---- range reads by a caller-held index (zj_index.h) ----
+// No kernel above is edited: the request kernel stands where zj_range_count_kernel stands, zj_range_scan_kernel runs with n := R, the entries of set A are written
+// one lane each, and zj_range_emit itself (with no interior entry to walk) writes set B and the copy runs of a request.
+size_t zjni_index_bytes(size_t n, size_t E) { return (size_t)zj_index_bytes(n, E); }
+// One wave per buffer: lanes stride its entries, a wave-wide AND gives valid[i] (zj_pieces_count_kernel's shape).
+__global__ __launch_bounds__(64) void zj_index_buffers_kernel(const u64* __restrict__ first, const u64* __restrict__ size, const u64* __restrict__ content, const u64* __restrict__ result,
+                                                              u32 n, u64 E, u64* __restrict__ valid) {
+    u32 const lane = threadIdx.x;
+    for (u32 i = blockIdx.x; i < n; i += gridDim.x) {
+        bool ok = zj_index_first_ok(first, i, E);
+        u64 const f0 = first[i], f1 = first[i + 1];
+        for (u64 e = f0 + lane; ok && e < f1; e += 64) ok = size[e] <= ZJ_INDEX_SIZE_MAX && content[e] <= ZJ_INDEX_SIZE_MAX;
+        ok = __ballot(!ok) == 0ull;
+        if (lane == 0) valid[i] = zj_index_valid(ok, result, i);
+    }
+}
+// workgroup 0: C[0 .. E] = exclusive prefix sums of the compressed sizes; workgroup 1: U of the content sizes (zj_range_scan_kernel's shape, E items)
+__global__ __launch_bounds__(ZJ_INDEX_SCAN_WG) void zj_index_scan_kernel(const u64* __restrict__ size, const u64* __restrict__ content, u64 E, u64* __restrict__ C, u64* __restrict__ U) {
+    __shared__ u64 part[ZJ_INDEX_SCAN_WG];
+    u32 const t = threadIdx.x;
+    const u64* const in = blockIdx.x ? content : size;
+    u64* const out = blockIdx.x ? U : C;
+    u64 const per = (E + ZJ_INDEX_SCAN_WG - 1u) / ZJ_INDEX_SCAN_WG, lo0 = (u64)t * per, lo = lo0 < E ? lo0 : E, hi = lo + per < E ? lo + per : E;
+    u64 sum = 0;
+    for (u64 i = lo; i < hi; i++) sum += zj_index_term(in[i]);
+    part[t] = sum;
+    __syncthreads();
+    for (u32 d = 1; d < ZJ_INDEX_SCAN_WG; d <<= 1) {
+        u64 const v = t >= d ? part[t - d] : 0;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    u64 run = t ? part[t - 1] : 0;
+    for (u64 i = lo; i < hi; i++) { out[i] = run; run += zj_index_term(in[i]); }
+    if (t == ZJ_INDEX_SCAN_WG - 1u) out[E] = part[ZJ_INDEX_SCAN_WG - 1u];
+}
+// one lane per entry: the content size of a piece from the cuts (or the fixed grid) its compress call took; an entry no buffer owns counts nothing
+__global__ __launch_bounds__(256) void zj_index_content_kernel(const u64* __restrict__ off, const u64* __restrict__ first, u32 n, u64 E, u64 chunk, const u64* __restrict__ cut,
+                                                               const u64* __restrict__ cutOff, u64* __restrict__ content) {
+    u64 const e = (u64)blockIdx.x * 256u + threadIdx.x;
+    if (e >= E) return;
+    content[e] = 0;
+    if (!n) return;
+    u64 const i = zj_entry_owner(first, n, e), f0 = first[i];
+    if (e < f0 || e >= first[i + 1]) return;
+    u64 const lo = off[i], hi = off[i + 1], size = hi > lo ? hi - lo : 0;
+    const u64* list = nullptr; u64 c = 0;
+    if (cut) { u64 const c0 = cutOff[i], c1 = cutOff[i + 1]; c = c1 > c0 ? c1 - c0 : 0; list = cut + c0; }
+    content[e] = zj_index_piece_content(size, chunk, list, c, e - f0);
+}
+// (the caller holds the device's BatchOrder)
+static size_t index_build_ordered(DevState* d, size_t n, const u64* d_first, const u64* d_size, const u64* d_content, const u64* d_result, size_t E, u64* d_index, hipStream_t st) {
+    u64* const first = d_index; u64* const valid = d_index + n + 1; u64* const C = d_index + 2 * n + 1; u64* const U = C + E + 1;
+    if (hipMemcpyAsync(first, d_first, (n + 1) * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (n) {
+        u32 const gridW = (u32)(n < (size_t)d->numCU * 8 ? n : (size_t)d->numCU * 8);
+        hipLaunchKernelGGL(zj_index_buffers_kernel, dim3(gridW), dim3(64), 0, st, d_first, d_size, d_content, d_result, (u32)n, (u64)E, valid);
+    }
+    hipLaunchKernelGGL(zj_index_scan_kernel, dim3(2), dim3(ZJ_INDEX_SCAN_WG), 0, st, d_size, d_content, (u64)E, C, U);
+    return hipGetLastError() == hipSuccess ? 0 : ZJNI_ERR(ZJNI_ERROR_no_device);
+}
+size_t zjni_index_from_sizes_device(size_t n, const uint64_t* d_piece_first, const uint64_t* d_piece_size, const uint64_t* d_piece_content, size_t E, void* d_index, void* stream) {
+    DevState* d = cur_state();
+    if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (n > 0xFFFFFFFFull || E > 0xFFFFFFFFull) return ZJNI_ERR(72);
+    if (!d_index || !d_piece_first || (E && (!d_piece_size || !d_piece_content))) return ZJNI_ERR(42);
+    BatchOrder order(d, stream);
+    return index_build_ordered(d, n, (const u64*)d_piece_first, (const u64*)d_piece_size, (const u64*)d_piece_content, nullptr, E, (u64*)d_index, (hipStream_t)stream);
+}
+size_t zjni_index_from_pieces_device(const uint64_t* d_src_off, size_t n, size_t chunkSize, const uint64_t* d_cut, const uint64_t* d_cut_off, const uint64_t* d_result,
+                                     const uint64_t* d_piece_first, const uint64_t* d_piece_size, size_t E, void* d_index, void* stream) {
+    DevState* d = cur_state();
+    if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (n > 0xFFFFFFFFull || E > 0xFFFFFFFFull) return ZJNI_ERR(72);
+    if (chunkSize < 256 || chunkSize > ZJNI_BLOCKSIZE_MAX || (d_cut && !d_cut_off)) return ZJNI_ERR(42);
+    if (!d_index || !d_piece_first || (n && !d_src_off) || (E && !d_piece_size)) return ZJNI_ERR(42);
+    hipStream_t const st = (hipStream_t)stream;
+    BatchOrder order(d, stream);
+    if (!frames_state(d)) return ZJNI_ERR(64);
+    size_t const r = frames_room(d, zj_up16(E * 8) + 16, 0, st);           // the content sizes, until the scan behind them has run (stream order)
+    if (r != 0) return r;
+    u64* const content = (u64*)d->framesBuf;
+    if (E) hipLaunchKernelGGL(zj_index_content_kernel, dim3((u32)((E + 255) / 256)), dim3(256), 0, st, (const u64*)d_src_off, (const u64*)d_piece_first, (u32)n, (u64)E, (u64)chunkSize,
+                              (const u64*)d_cut, (const u64*)d_cut_off, content);
+    return index_build_ordered(d, n, (const u64*)d_piece_first, (const u64*)d_piece_size, content, (const u64*)d_result, E, (u64*)d_index, st);
+}
+
+// per request: [rec R][ireq R][bad R][q 5 x R][scan 5 x (R + 1)][totals 5] — the range layer's, with the request's place in the index and its mark beside the record
+// one lane per request: rules 1-4 by bisection
+__global__ __launch_bounds__(64) void zj_index_request_kernel(const u64* __restrict__ idx, u64 n, u64 E, const u64* __restrict__ off, const u64* __restrict__ req, const u64* __restrict__ dstOff,
+                                                              ZRRec* __restrict__ rec, ZIReq* __restrict__ ireq, u32* __restrict__ bad, u64* __restrict__ q, u64* __restrict__ total, u32 R) {
+    u64 const i = (u64)blockIdx.x * 64u + threadIdx.x;
+    if (i >= R) return;
+    u64 const dlo = dstOff[i], dhi = dstOff[i + 1];
+    ZRRec r; ZIReq ir; u64 qq[5];
+    zj_index_request(idx, n, E, off, req[3 * i], req[3 * i + 1], req[3 * i + 2], dhi > dlo ? dhi - dlo : 0, r, ir, qq);
+    rec[i] = r; ireq[i] = ir; bad[i] = 0;
+    for (u32 k = 0; k < 5; k++) q[(u64)k * R + i] = qq[k];
+    if (total) total[i] = r.total;
+}
+// one lane per entry of set A: an interior entry whose sums do not ascend inside its request's run marks the request
+__global__ __launch_bounds__(ZJ_INDEX_EMIT_WG) void zj_index_check_kernel(const u64* __restrict__ idx, u64 n, u64 E, const ZRRec* __restrict__ rec, const ZIReq* __restrict__ ireq,
+                                                                          const u64* __restrict__ fA, u32 R, u64 EA, u32* __restrict__ bad) {
+    u64 const g = (u64)blockIdx.x * ZJ_INDEX_EMIT_WG + threadIdx.x;
+    if (g >= EA) return;
+    u64 const r = zj_entry_owner(fA, R, g), j = g - fA[r], m = fA[r + 1] - fA[r] - 1u;
+    if (j >= m || rec[r].status != ZJ_RANGE_SELECTED) return;
+    ZIView const v = zj_index_view(idx, n, E);
+    if (!zj_index_entry_ok(v.C, v.U, rec[r], ireq[r], j)) bad[r] = 1u;
+}
+// one lane per entry of set A, the closing entries included: the owner by bisection over the scanned counts, the offsets from C and U alone
+__global__ __launch_bounds__(ZJ_INDEX_EMIT_WG) void zj_index_emit_kernel(const u64* __restrict__ idx, u64 n, u64 E, const ZRRec* __restrict__ rec, const ZIReq* __restrict__ ireq,
+                                                                         const u32* __restrict__ bad, const u64* __restrict__ scan, const u64* __restrict__ dstOff, u32 R, u64 EA,
+                                                                         u64* __restrict__ srcA, u64* __restrict__ dstA) {
+    u64 const g = (u64)blockIdx.x * ZJ_INDEX_EMIT_WG + threadIdx.x;
+    if (g >= EA) return;
+    const u64* const fA = scan; const u64* const cA = scan + 2 * ((u64)R + 1u);
+    u64 const r = zj_entry_owner(fA, R, g);
+    ZIView const v = zj_index_view(idx, n, E);
+    u64 s, dd;
+    zj_index_entry(v.C, v.U, rec[r], ireq[r], bad[r] != 0u, g - fA[r], cA[r], dstOff[r], &s, &dd);
+    srcA[g] = s; dstA[g] = dd;
+}
+// one lane per request, behind the emit kernel: set B and the copy runs as zj_range_emit writes them for a buffer with no interior entry to walk; the lane of the
+// last request closes the arrays
+__global__ __launch_bounds__(64) void zj_index_edges_kernel(const ZRRec* __restrict__ rec, const ZIReq* __restrict__ ireq, const u64* __restrict__ scan, const u64* __restrict__ dstOff, u32 R,
+                                                            u64* __restrict__ srcA, u64* __restrict__ dstA, u64* __restrict__ srcB, u64* __restrict__ dstB,
+                                                            ZRCopy* __restrict__ in, ZRCopy* __restrict__ out) {
+    u64 const i = (u64)blockIdx.x * 64u + threadIdx.x;
+    if (i >= R) return;
+    u64 const n1 = (u64)R + 1u;
+    const u64* const fA = scan; const u64* const fB = scan + n1; const u64* const cA = scan + 2 * n1; const u64* const cB = scan + 3 * n1; const u64* const eB = scan + 4 * n1;
+    u64 const a1 = fA[i + 1], b0 = fB[i];
+    ZRRec const r = rec[i];
+    ZRCopy cin[3], cout[2];
+    u64 closeSrc, closeDst;
+    zj_range_emit(nullptr, 0, r, ireq[i].srcLo, dstOff[i], 0u, cA[i], cA[R] + cB[i], eB[i], &closeSrc, &closeDst, srcB + b0, dstB + b0, cin, cout);
+    in[i] = cin[0]; in[(u64)R + 2 * i] = cin[1]; in[(u64)R + 2 * i + 1] = cin[2];
+    out[2 * i] = cout[0]; out[2 * i + 1] = cout[1];
+    if (i + 1 == R) { srcA[a1] = cA[R]; dstA[a1] = dstA[a1 - 1]; srcB[fB[R]] = cA[R] + cB[R]; dstB[fB[R]] = eB[R]; }
+}
+// One wave per request, zj_range_finish_kernel with one rule more: an entry that decoded without error to another size than the index says answers 20, as does a
+// request an entry marked.  stat[8 .. 12).
+__global__ __launch_bounds__(64) void zj_index_finish_kernel(const u64* __restrict__ idx, u64 n, u64 E, const ZRRec* __restrict__ rec, const ZIReq* __restrict__ ireq, const u32* __restrict__ bad,
+                                                             const u64* __restrict__ scan, const u64* __restrict__ resA, const u64* __restrict__ resB,
+                                                             u64* __restrict__ result, u32 R, ZRCopy* __restrict__ out, u32* stat) {
+    u32 const lane = threadIdx.x;
+    const u64* const U = zj_index_view(idx, n, E).U;
+    for (u32 i = blockIdx.x; i < R; i += gridDim.x) {
+        u32 const status = rec[i].status, e = rec[i].edges, frames = rec[i].frames;
+        if (status != ZJ_RANGE_SELECTED) {
+            if (lane == 0) { result[i] = status == ZJ_RANGE_NOTHING ? 0 : ZJ_ERR64(status); atomicAdd(&stat[status == ZJ_RANGE_NOTHING ? 8 : 11], 1u); }
+            continue;
+        }
+        u64 const a0 = scan[i], m = scan[i + 1] - a0 - 1u, b0 = scan[(u64)R + 1u + i], e0 = ireq[i].e0;
+        u64 err = bad[i] ? ZJ_ERR64(ZJ_E_CORRUPTION) : 0;
+        if (!err && (e & 1u)) err = zj_index_verdict(resB[b0], rec[i].fcsF);
+        for (u64 base = 0; base < m && !err; base += 64) {
+            u64 const k = base + lane;
+            u64 const v = k < m ? zj_index_verdict(resA[a0 + k], U[e0 + k + 1] - U[e0 + k]) : 0;
+            unsigned long long const mask = __ballot(v != 0);
+            if (mask) err = __shfl(v, (int)(__ffsll((long long)mask) - 1), 64);
+        }
+        if (!err && (e & 2u)) err = zj_index_verdict(resB[b0 + (e & 1u)], rec[i].fcsL);
+        if (lane == 0) {
+            result[i] = err ? err : rec[i].hi - rec[i].lo;
+            if (err) { out[2 * (u64)i].len = 0; out[2 * (u64)i + 1].len = 0; }
+            atomicAdd(&stat[err ? 11 : 8], 1u); atomicAdd(&stat[9], frames); atomicAdd(&stat[10], zj_range_edge_count(e));
+        }
+    }
+}
+size_t zjni_decompress_index_range_batch_device(const void* d_src, const uint64_t* d_src_off, size_t n, const void* d_index, size_t E, const uint64_t* d_req,
+                                                void* d_dst, const uint64_t* d_dst_off, uint64_t* d_result, uint64_t* d_total, size_t R,
+                                                const zjni_ddict* ddict, void* stream) {
+    if (ddict && ddict->ordinal != t_dev && t_dev >= 0) return ZJNI_ERR(32);      // digested on another device
+    DevState* d = cur_state();
+    if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (n > 0xFFFFFFFFull || E > 0xFFFFFFFFull || R > 0xFFFFFFFFull) return ZJNI_ERR(72);
+    hipStream_t const st = (hipStream_t)stream;
+    BatchOrder order(d, stream);
+    if (!frames_state(d)) return ZJNI_ERR(64);
+    if (hipMemsetAsync(d->framesStat + 8, 0, 16, st) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (R == 0) return 0;
+    if (!d_index) return ZJNI_ERR(42);
+    const u64* const idx = (const u64*)d_index;
+    size_t const oRec = 0, oReq = zj_up16(R * sizeof(ZRRec)), oBad = oReq + zj_up16(R * sizeof(ZIReq)), oQ = oBad + zj_up16(R * 4), oScan = oQ + zj_up16(5 * R * 8),
+                 oTot = oScan + zj_up16(5 * (R + 1) * 8), perReq = oTot + 64;
+    size_t r = frames_room(d, perReq, 0, st);
+    if (r != 0) return r;
+    u32 const gridR = (u32)((R + 63) / 64);
+    hipLaunchKernelGGL(zj_index_request_kernel, dim3(gridR), dim3(64), 0, st, idx, (u64)n, (u64)E, (const u64*)d_src_off, (const u64*)d_req, (const u64*)d_dst_off,
+                       (ZRRec*)(d->framesBuf + oRec), (ZIReq*)(d->framesBuf + oReq), (u32*)(d->framesBuf + oBad), (u64*)(d->framesBuf + oQ), (u64*)d_total, (u32)R);
+    hipLaunchKernelGGL(zj_range_scan_kernel, dim3(5), dim3(1024), 0, st, (const u64*)(d->framesBuf + oQ), (u64*)(d->framesBuf + oScan), (u64*)(d->framesBuf + oTot), (u32)R);
+    // the entry's only host wait, as in the walked entry: the five totals in one copy of 40 bytes (the pipelines size their launches on the host)
+    if (hipMemcpyAsync((void*)d->framesE, d->framesBuf + oTot, 40, hipMemcpyDeviceToHost, st) != hipSuccess || hipEventRecord(d->evFramesE, st) != hipSuccess
+        || hipEventSynchronize(d->evFramesE) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    u64 const EA = d->framesE[0], EB = d->framesE[1], CA = d->framesE[2], CB = d->framesE[3], SB = d->framesE[4];
+    if (EA > 0xFFFFFFFFull) return ZJNI_ERR(72);
+    if (EA < R || EB > 2 * (u64)R) return ZJNI_ERR(ZJNI_ERROR_no_device);          // (every request has its closing entry and at most two edges)
+    // per entry and per run: [srcA EA + 1][dstA EA + 1][resA EA][srcB EB + 1][dstB EB + 1][resB EB][in 3R][out 2R][compact bytes CA + CB][edge scratch SB]
+    size_t const oSrcA = perReq, oDstA = oSrcA + zj_up16((EA + 1) * 8), oResA = oDstA + zj_up16((EA + 1) * 8), oSrcB = oResA + zj_up16(EA * 8 + 8),
+                 oDstB = oSrcB + zj_up16((EB + 1) * 8), oResB = oDstB + zj_up16((EB + 1) * 8), oIn = oResB + zj_up16(EB * 8 + 8), oOut = oIn + zj_up16(3 * R * sizeof(ZRCopy)),
+                 oComp = oOut + zj_up16(2 * R * sizeof(ZRCopy)), oEdge = oComp + zj_up16(CA + CB) + 16, total = oEdge + zj_up16(SB) + 16;
+    if (CA + CB < CA || total < oComp || total < SB) return ZJNI_ERR(64);
+    if ((r = frames_room(d, total, perReq, st)) != 0) return r;
+    u8* const fb = d->framesBuf;
+    const ZRRec* const rec = (const ZRRec*)(fb + oRec); const ZIReq* const ireq = (const ZIReq*)(fb + oReq); u32* const bad = (u32*)(fb + oBad);
+    const u64* const scan = (const u64*)(fb + oScan);
+    ZRCopy* const in = (ZRCopy*)(fb + oIn); ZRCopy* const out = (ZRCopy*)(fb + oOut);
+    u32 const gridA = (u32)((EA + ZJ_INDEX_EMIT_WG - 1u) / ZJ_INDEX_EMIT_WG);
+    if (EA > R) hipLaunchKernelGGL(zj_index_check_kernel, dim3(gridA), dim3(ZJ_INDEX_EMIT_WG), 0, st, idx, (u64)n, (u64)E, rec, ireq, scan, (u32)R, EA, bad);
+    hipLaunchKernelGGL(zj_index_emit_kernel, dim3(gridA), dim3(ZJ_INDEX_EMIT_WG), 0, st, idx, (u64)n, (u64)E, rec, ireq, (const u32*)bad, scan, (const u64*)d_dst_off, (u32)R, EA,
+                       (u64*)(fb + oSrcA), (u64*)(fb + oDstA));
+    hipLaunchKernelGGL(zj_index_edges_kernel, dim3(gridR), dim3(64), 0, st, rec, ireq, scan, (const u64*)d_dst_off, (u32)R, (u64*)(fb + oSrcA), (u64*)(fb + oDstA),
+                       (u64*)(fb + oSrcB), (u64*)(fb + oDstB), in, out);
+    u64 const tilesIn = (CA + CB + ZJ_RANGE_TILE - 1) / ZJ_RANGE_TILE, tilesOut = (SB + ZJ_RANGE_TILE - 1) / ZJ_RANGE_TILE;
+    if (tilesIn > 0x7FFFFFFFull || tilesOut > 0x7FFFFFFFull) return ZJNI_ERR(64);
+    if (tilesIn) hipLaunchKernelGGL(zj_range_gather_kernel, dim3((u32)tilesIn), dim3(256), 0, st, (const ZRCopy*)in, (u64)(3 * R), (const u8*)d_src, fb + oComp, 1u, CA + CB);
+    if (hipGetLastError() != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (EA > R && (r = decompress_chunked_ordered(fb + oComp, (const u64*)(fb + oSrcA), d_dst, (const u64*)(fb + oDstA), (u64*)(fb + oResA), (size_t)EA, ddict, stream)) != 0) return r;
+    if (EB && (r = decompress_chunked_ordered(fb + oComp, (const u64*)(fb + oSrcB), fb + oEdge, (const u64*)(fb + oDstB), (u64*)(fb + oResB), (size_t)EB, ddict, stream)) != 0) return r;
+    u32 const gridF = (u32)(R < (size_t)d->numCU * 8 ? R : (size_t)d->numCU * 8);
+    hipLaunchKernelGGL(zj_index_finish_kernel, dim3(gridF), dim3(64), 0, st, idx, (u64)n, (u64)E, rec, ireq, (const u32*)bad, scan, (const u64*)(fb + oResA), (const u64*)(fb + oResB),
+                       (u64*)d_result, (u32)R, out, d->framesStat);
+    if (tilesOut) hipLaunchKernelGGL(zj_range_gather_kernel, dim3((u32)tilesOut), dim3(256), 0, st, (const ZRCopy*)out, (u64)(2 * R), (const u8*)(fb + oEdge), (u8*)d_dst, 0u, SB);
+    return hipGetLastError() == hipSuccess ? 0 : ZJNI_ERR(ZJNI_ERROR_no_device);
+}
+int zjni_last_index_range(unsigned* out4) {
+    DevState* d = cur_state();
+    if (!d || !out4) return -(int)ZJNI_ERROR_no_device;
+    u32 h[4] = {0, 0, 0, 0};
+    if (hipDeviceSynchronize() != hipSuccess || (d->framesStat && hipMemcpy(h, d->framesStat + 8, sizeof h, hipMemcpyDeviceToHost) != hipSuccess)) return -(int)ZJNI_ERROR_no_device;
+    for (int k = 0; k < 4; k++) out4[k] = h[k];
+    return 0;
+}
+
 // ---- chunked compress ----
 size_t zjni_compressBound_chunked(size_t srcSize, size_t chunkSize) {
     if (chunkSize < 256 || chunkSize > ZJNI_BLOCKSIZE_MAX) return ZJNI_ERR(42);
@@ -4284,6 +4522,58 @@ size_t zjni_decompress_frames_range_usingDDict(void* dst, size_t dstCap, const v
     if (hipMemcpyAsync(sl->hPinned + 32, sl->dStage + 32, 32, hipMemcpyDeviceToHost, hst) != hipSuccess || hipStreamSynchronize(hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
     size_t const res = (size_t)h[4];
     if (total) *total = h[7];
+    if (zjni_isError(res) || res == 0) return res;
+    if (res > dstCap) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (hipMemcpyAsync(sl->hPinned + oDst, sl->dStage + oDst, res, hipMemcpyDeviceToHost, hst) != hipSuccess || hipStreamSynchronize(hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    memcpy(dst, sl->hPinned + oDst, res);
+    return res;
+}
+
+// The indexed form for one host buffer: rules 1-4 run here, on the host, with the functions the request kernel runs; only the selected entries' bytes and their slice
+// of the index cross the link, and the device entry answers the range shifted by the content before the first selected entry.  The slot's first 64 bytes are
+// [srcOff 2][dstOff 2][result 1][request 3], then [index of 1 buffer and m entries][the selected source bytes][dst].
+size_t zjni_decompress_index_range(void* dst, size_t dstCap, const void* src, size_t srcSize, unsigned long long lo, unsigned long long len,
+                                   const uint64_t* pieceSize, const uint64_t* pieceContent, size_t nPieces, unsigned long long* total, const zjni_ddict* ddict) {
+    DevState* d = cur_state();
+    if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (total) *total = ZJ_FI_ERROR;
+    if ((u64)dstCap > len) dstCap = (size_t)len;
+    if (srcSize > ((size_t)1 << 46) || dstCap > ((size_t)1 << 46) || nPieces > 0xFFFFFFFFull) return ZJNI_ERR(64);
+    if ((srcSize && !src) || (dstCap && !dst) || (nPieces && (!pieceSize || !pieceContent))) return ZJNI_ERR(72);
+    // the whole buffer's index in host memory: one buffer, nPieces entries
+    std::vector<u64> hidx((size_t)zj_index_words(1, nPieces));
+    u64* const C = hidx.data() + 3; u64* const U = C + nPieces + 1;
+    bool legal = true;
+    hidx[0] = 0; hidx[1] = nPieces; C[0] = U[0] = 0;
+    for (size_t e = 0; e < nPieces; e++) {
+        legal = legal && pieceSize[e] <= ZJ_INDEX_SIZE_MAX && pieceContent[e] <= ZJ_INDEX_SIZE_MAX;
+        C[e + 1] = C[e] + zj_index_term(pieceSize[e]); U[e + 1] = U[e] + zj_index_term(pieceContent[e]);
+    }
+    hidx[2] = zj_index_valid(legal, nullptr, 0);
+    u64 const hoff[2] = {0, (u64)srcSize};
+    ZRRec rec; ZIReq ir; u64 q[5];
+    zj_index_request(hidx.data(), 1, nPieces, hoff, 0, lo, len, dstCap, rec, ir, q);
+    if (total) *total = rec.total;
+    if (rec.status == ZJ_RANGE_NOTHING) return 0;
+    if (rec.status != ZJ_RANGE_SELECTED) return ZJNI_ERR(rec.status);
+    u64 const eF = ir.e0 - (rec.edges & 1u), m = rec.frames, cLo = C[eF], bytes = C[eF + m] - cLo, uLo = U[eF], want = rec.hi - rec.lo;
+    size_t const idxBytes = (size_t)zj_index_bytes(1, m), oIdx = 64, oSrc = oIdx + idxBytes, oDst = oSrc + zj_up16(bytes), all = oDst + want + 16;
+    SlotLock slotLock(d); StageSlot* const sl = slotLock.s;
+    if (!ensure_staging(sl, all)) return ZJNI_ERR(ZJNI_ERROR_unsupported);
+    hipStream_t const hst = sl->hostK;
+    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drainOnExit{hst};
+    u64* const h = (u64*)sl->hPinned;
+    h[0] = 0; h[1] = bytes; h[2] = 0; h[3] = want; h[4] = 0; h[5] = 0; h[6] = rec.lo - uLo; h[7] = want;
+    u64* const hi = (u64*)(sl->hPinned + oIdx);
+    hi[0] = 0; hi[1] = m; hi[2] = 0;
+    for (u64 k = 0; k <= m; k++) { hi[3 + k] = C[eF + k] - cLo; hi[3 + m + 1 + k] = U[eF + k] - uLo; }
+    memcpy(sl->hPinned + oSrc, (const u8*)src + cLo, bytes);
+    if (hipMemcpyAsync(sl->dStage, sl->hPinned, oSrc + bytes, hipMemcpyHostToDevice, hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    u64* const dW = (u64*)sl->dStage;
+    size_t const r = zjni_decompress_index_range_batch_device(sl->dStage + oSrc, dW, 1, sl->dStage + oIdx, (size_t)m, dW + 5, sl->dStage + oDst, dW + 2, dW + 4, nullptr, 1, ddict, hst);
+    if (zjni_isError(r)) return r;
+    if (hipMemcpyAsync(sl->hPinned + 32, sl->dStage + 32, 8, hipMemcpyDeviceToHost, hst) != hipSuccess || hipStreamSynchronize(hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    size_t const res = (size_t)h[4];
     if (zjni_isError(res) || res == 0) return res;
     if (res > dstCap) return ZJNI_ERR(ZJNI_ERROR_no_device);
     if (hipMemcpyAsync(sl->hPinned + oDst, sl->dStage + oDst, res, hipMemcpyDeviceToHost, hst) != hipSuccess || hipStreamSynchronize(hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
