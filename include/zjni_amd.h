@@ -450,7 +450,30 @@ size_t zjni_decompress_frames_range_usingDDict(void* dst, size_t dstCapacity, co
  * entries handed to the decoder, out4[2] edge entries among them, out4[3] requests that answered an error.
  * zjni_decompress_index_range: the blocking form for ONE host buffer with its nPieces sizes and content sizes in host memory.  It selects on the host by the same
  * rules and sends ONLY the selected entries' compressed bytes and their slice of the index across the link; answer, bytes and *total (may be NULL) are those of
- * staging the whole buffer. */
+ * staging the whole buffer.
+ *
+ * THE INDEX FROM THE FRAMES ALONE, for whoever holds only the bytes (another process, a file read back, frames of the reference or of pzstd): two walks over the
+ * frame headers, once, and every later read is the indexed one.  One entry is one frame; a skippable frame is an entry of content 0.
+ * A buffer is INDEXABLE by exactly rule 1 of the ranged entry above, in walk order, first failure first (a source above 2^32 - 1 bytes: 14; a step's error: that
+ * step's code; a zstd frame without a content size: 14; content sizes summing past 64 bits: 14) WITH ONE ADDITION the entry format forces: a frame that records
+ * a content size above 2^32 - 1 answers 14 at that frame.  It is the only place where the ranged entry and a read by this index may answer differently.  A
+ * buffer that is not indexable owns 0 entries and carries its code in valid[i]: every read of it answers that code.  An empty buffer owns 0 entries, valid 0.
+ *  zjni_index_count_frames_device: the first walk, one lane per buffer, and the exclusive scan: d_piece_first[i] = the entries before buffer i,
+ *    d_piece_first[n] = E.  The caller reads those eight bytes and allocates zjni_index_bytes(n, E).
+ *  zjni_index_from_frames_device: the second walk writes each buffer's sizes at d_piece_first[i], then valid, then C and U by the builders' scan.  d_piece_size
+ *    and d_piece_content ([E] each, either may be NULL) receive the entries' compressed and content sizes: the compact form a caller stores beside the file,
+ *    from which zjni_index_from_sizes_device rebuilds the index without the bytes.  The second walk trusts nothing of the first: it is bounded by
+ *    d_piece_first[i + 1] - d_piece_first[i] and writes inside that extent only; a d_piece_first that does not ascend at i or exceeds E gives valid[i] = 42, and so
+ *    does a walk that does not end at the buffer's end with exactly that count (the bytes changed between the calls, or the array is not the first call's); the
+ *    buffer's entries are then written as 0 and the other buffers are not affected.
+ * Both are asynchronous on `stream` and wait for nothing on the host; n == 0 and E == 0 are legal; n or E above 2^32 - 1: 72.
+ * zjni_index_from_frames: the same walk for ONE host buffer, pure host code, no device: pieceSize[] and pieceContent[] as zjni_decompress_index_range takes
+ * them and *nPieces = the entry count.  Returns 0; the buffer's code when it is not indexable (*nPieces = 0); 70 with *nPieces = the count needed when
+ * `capacity` is below it (capacity == 0 with NULL arrays is the counting call).  A host reader of a file then uploads only the frames a range selects. */
+size_t zjni_index_count_frames_device(const void* d_src, const uint64_t* d_src_off /* [n + 1] */, size_t n, uint64_t* d_piece_first /* [n + 1] out */, void* stream);
+size_t zjni_index_from_frames_device(const void* d_src, const uint64_t* d_src_off /* [n + 1] */, size_t n, const uint64_t* d_piece_first /* [n + 1] */, size_t E,
+                                     void* d_index, uint64_t* d_piece_size /* [E] out, or NULL */, uint64_t* d_piece_content /* [E] out, or NULL */, void* stream);
+size_t zjni_index_from_frames(const void* src, size_t srcSize, uint64_t* pieceSize, uint64_t* pieceContent, size_t capacity, size_t* nPieces);
 size_t zjni_index_bytes(size_t n, size_t E);
 size_t zjni_index_from_sizes_device(size_t n, const uint64_t* d_piece_first /* [n + 1] */, const uint64_t* d_piece_size /* [E] */,
                                     const uint64_t* d_piece_content /* [E] */, size_t E, void* d_index, void* stream);

@@ -273,6 +273,13 @@ def lib():
         L.zjni_last_index_range.argtypes = [C.POINTER(C.c_uint)]
         L.zjni_decompress_index_range.restype = sz
         L.zjni_decompress_index_range.argtypes = [vp, sz, vp, sz, C.c_ulonglong, C.c_ulonglong, vp, vp, sz, C.POINTER(C.c_ulonglong), vp]
+    if hasattr(L, "zjni_index_from_frames_device"):      # the index from the frames alone
+        L.zjni_index_count_frames_device.restype = sz
+        L.zjni_index_count_frames_device.argtypes = [vp, vp, sz, vp, vp]
+        L.zjni_index_from_frames_device.restype = sz
+        L.zjni_index_from_frames_device.argtypes = [vp, vp, sz, vp, sz, vp, vp, vp, vp]
+        L.zjni_index_from_frames.restype = sz
+        L.zjni_index_from_frames.argtypes = [vp, sz, vp, vp, sz, C.POINTER(sz)]
     if hasattr(L, "zjni_test_compress_records_batch_device"):      # test entry: the entropy stage on the caller's records
         L.zjni_test_compress_records_batch_device.restype = sz
         L.zjni_test_compress_records_batch_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, sz, C.c_int, C.c_int, C.c_int, C.c_int, vp]
@@ -305,6 +312,7 @@ EXPORTS = ("zjni_version", "zjni_device_count", "zjni_init", "zjni_shutdown", "z
            "zjni_decompress_frames_usingDDict", "zjni_decompress_frames_range_usingDDict",
            "zjni_index_bytes", "zjni_index_from_sizes_device", "zjni_index_from_pieces_device", "zjni_decompress_index_range_batch_device",
            "zjni_last_index_range", "zjni_decompress_index_range",
+           "zjni_index_count_frames_device", "zjni_index_from_frames_device", "zjni_index_from_frames",
            "zjni_test_compress_records_batch_device")
 
 
@@ -326,6 +334,22 @@ def decompress_index_range(src, lo, length, piece_size, piece_content, dictionar
     if lib().zjni_isError(r):
         raise ZstdException(r)
     return dst.raw[:r], total.value
+
+
+def index_from_frames(src):
+    """zjni_index_from_frames: (piece_size, piece_content) of ONE host buffer of concatenated frames, one entry a frame, from its headers alone — what
+    decompress_index_range() takes.  Pure host code: no device is needed.  Raises ZstdException with the buffer's code when it cannot be indexed."""
+    buf = bytes(src)
+    n = C.c_size_t(0)
+    r = lib().zjni_index_from_frames(buf, len(buf), None, None, 0, C.byref(n))
+    if lib().zjni_isError(r) and lib().zjni_getErrorCode(r) != 70:
+        raise ZstdException(r)
+    count = n.value
+    sizes, contents = (C.c_uint64 * max(count, 1))(), (C.c_uint64 * max(count, 1))()
+    r = lib().zjni_index_from_frames(buf, len(buf), sizes, contents, count, C.byref(n))
+    if lib().zjni_isError(r):
+        raise ZstdException(r)
+    return list(sizes[:count]), list(contents[:count])
 
 
 # --------------------------------------------------------------------------- Java API mirror --

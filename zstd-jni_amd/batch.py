@@ -316,6 +316,32 @@ def index_from_pieces(src_off, results, piece_first, piece_size, chunk=1 << 16, 
     return index
 
 
+def index_from_frames(src_blob, src_off, index=None, sizes=False):
+    """The prepared index of n buffers of concatenated frames from their bytes alone, for a reader who did not compress them: zjni_index_count_frames_device (a walk
+    over the frame headers, one entry a frame), one read of E on the host — the only wait — and zjni_index_from_frames_device (the second walk and the scan), both on
+    the current stream.  A buffer the ranged entry would not index (or with a frame whose content size exceeds 2^32 - 1) owns no entry and carries its code: every
+    read of it answers that code.  Returns (index, E, piece_first int64[n + 1]); with sizes=True also piece_size int64[E] and piece_content int64[E], the compact
+    form to store beside the bytes: index_from_sizes() rebuilds the index from them.  `index`: an int64 tensor of at least index_bytes(n, E) bytes to build into."""
+    n = src_off.numel() - 1
+    dev = src_blob.device
+    piece_first = torch.empty(n + 1, dtype=torch.int64, device=dev)
+    _check(lib().zjni_index_count_frames_device(src_blob.data_ptr(), src_off.data_ptr(), n, piece_first.data_ptr(), _stream_ptr()))
+    entries = int(piece_first[n].item())
+    if index is None:
+        index = _index_tensor(n, entries, dev)
+    elif index.numel() * 8 < index_bytes(n, entries):
+        raise ValueError("index_from_frames: the index tensor is smaller than index_bytes(n, E)")
+    piece_size = piece_content = None
+    if sizes:
+        piece_size = torch.empty(max(entries, 1), dtype=torch.int64, device=dev)[:entries]
+        piece_content = torch.empty(max(entries, 1), dtype=torch.int64, device=dev)[:entries]
+    _check(lib().zjni_index_from_frames_device(src_blob.data_ptr(), src_off.data_ptr(), n, piece_first.data_ptr(), entries, index.data_ptr(),
+                                               piece_size.data_ptr() if sizes and entries else None, piece_content.data_ptr() if sizes and entries else None, _stream_ptr()))
+    if sizes:
+        return index, entries, piece_first, piece_size, piece_content
+    return index, entries, piece_first
+
+
 def decompress_index_range(src_blob, src_off, index, entries, requests, dst_blob, dst_off, results=None, totals=None, dictionary=None):
     """Enqueue zjni_decompress_index_range_batch_device on the current stream: `requests` is an int64[R, 3] (or [3R]) tensor of (buffer, lo, len); request r leaves
     the decoded bytes [lo, lo + len) of that buffer, clamped to its content, at dst_off[r].  The frames are found by bisection in `index` (index_from_sizes /

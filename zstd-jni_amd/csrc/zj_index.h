@@ -1,6 +1,7 @@
 // zj_index.h — range reads by a caller-held index instead of a walk over the frame headers: the prepared index, the request that finds its entries by bisection,
 // and the entries of set A one lane each.  Arithmetic only, host and device (zjni_index_from_*_device, zjni_decompress_index_range_batch_device; the kernels are in
-// zj_kernels.hip beside the range layer).
+// zj_kernels.hip beside the range layer).  The index is built from the sizes the compress call returned, or from the frames alone by a walk over their headers
+// (zj_index_walk: zjni_index_count_frames_device, zjni_index_from_frames_device, zjni_index_from_frames).
 //
 // THE INDEX of n buffers and E entries is (2n + 1) + 2(E + 1) words of 64 bits in the caller's device memory:
 //   first[n + 1]   entries before each buffer           valid[n]   0, or the error code that answers for the buffer (2 .. 2^32 - 1)
@@ -43,6 +44,46 @@ ZJ_HD u64 zj_index_piece_content(u64 size, u64 chunk, const u64* cut, u64 c, u64
     if (k > c) return 0;
     u64 const lo = k ? cut[k - 1] : 0, hi = k < c ? cut[k] : size;
     return hi > lo ? hi - lo : 0;
+}
+
+// ---- the index from the frames alone (zjni_index_count_frames_device, zjni_index_from_frames_device, zjni_index_from_frames) ----
+// The walk of buffer [p, p + n): its verdict (0: indexable, else the code that answers for it) and, in *entries, its entry count — one entry a frame, a
+// skippable frame an entry of content 0; a buffer that is not indexable has 0 entries, as has an empty one.  The first min(frames passed, cap) frames'
+// compressed sizes and content sizes go to size[] and content[] (cap == 0: nothing is written, the counting call), and *wrote says how many did.
+// The verdict is rule 1 of the ranged entry (zj_range_count) in walk order, first failure first: a source above ZJ_FRAMES_SRC_MAX 14, a step's error that
+// step's code, a zstd frame without a content size 14, content sizes summing past 64 bits 14.  ONE ADDITION, which the index's entry format forces
+// (ZJ_INDEX_SIZE_MAX): a frame that records a content size above 2^32 - 1 answers 14 at that frame.  It is the only place where the walked ranged entry and
+// a read by the walk-built index may answer differently for the same bytes.  (A frame's compressed size cannot exceed the maximum: the source does not.)
+ZJ_HD u32 zj_index_walk(const u8* p, u64 n, u64 cap, u64* size, u64* content, u64* entries, u64* wrote) {
+    *entries = 0; *wrote = 0;
+    if (n > ZJ_FRAMES_SRC_MAX) return ZJ_E_FRAMEPARAM_UNSUPPORTED;
+    ZFStep s;
+    u64 pos = 0, P = 0, k = 0;
+    ZJ_NO_UNROLL
+    while (pos < n) {
+        zj_frame_step(p + pos, n - pos, s);
+        if (zj_fi_is_err(s.csize)) return (u32)((u64)0 - s.csize);
+        if (!s.skippable && s.fcs == ZJ_FI_UNKNOWN) return ZJ_E_FRAMEPARAM_UNSUPPORTED;
+        u64 const fcs = s.skippable ? 0 : s.fcs;
+        if (fcs > ZJ_INDEX_SIZE_MAX || P + fcs < P) return ZJ_E_FRAMEPARAM_UNSUPPORTED;
+        if (k < cap) { size[k] = s.csize; content[k] = fcs; *wrote = k + 1; }
+        P += fcs; pos += s.csize; k++;
+    }
+    *entries = k;
+    return 0;
+}
+// The second walk of buffer i = [p, p + n), whose entries lie at first[i] .. first[i + 1] of size[E] and content[E]: valid[i].  It trusts nothing of the first
+// walk, whatever the bytes say now: a first[] that does not ascend at i or ends beyond E answers 42 and writes nothing (zj_index_first_ok); the walk writes
+// inside the buffer's own extent only; one that does not end at the buffer's end with exactly first[i + 1] - first[i] entries answers 42, and what it wrote is
+// written again as 0.  (A buffer that is not indexable owns no entry and keeps its verdict.)
+ZJ_HD u64 zj_index_frames_emit(const u8* p, u64 n, const u64* first, u64 i, u64 E, u64* size, u64* content) {
+    if (!zj_index_first_ok(first, i, E)) return 42u;
+    u64 const f0 = first[i], cap = first[i + 1] - f0;
+    u64 entries, wrote;
+    u32 const verdict = zj_index_walk(p, n, cap, size + f0, content + f0, &entries, &wrote);
+    if (verdict ? cap == 0 : entries == cap) return verdict;
+    for (u64 k = 0; k < wrote; k++) { size[f0 + k] = 0; content[f0 + k] = 0; }
+    return 42u;
 }
 
 // ---- the request ----

@@ -4052,6 +4052,69 @@ size_t zjni_index_from_pieces_device(const uint64_t* d_src_off, size_t n, size_t
     return index_build_ordered(d, n, (const u64*)d_piece_first, (const u64*)d_piece_size, content, (const u64*)d_result, E, (u64*)d_index, st);
 }
 
+// ---- the index from the frames alone: two walks over the headers with a scan between them, as the frames layer counts and emits ----
+// first walk, one lane per buffer as zj_frames_count_kernel walks: cnt[i] = entries of buffer i (0: empty, or not indexable)
+__global__ __launch_bounds__(64) void zj_index_walk_count_kernel(const u8* __restrict__ src, const u64* __restrict__ off, u64* __restrict__ cnt, u32 n) {
+    u64 const i = (u64)blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    u64 const lo = off[i], hi = off[i + 1];
+    u64 entries, wrote;
+    (void)zj_index_walk(src + lo, hi > lo ? hi - lo : 0, 0, nullptr, nullptr, &entries, &wrote);
+    cnt[i] = entries;
+}
+// second walk: the sizes of buffer i at first[i], inside its own extent of the E entries, and valid[i]
+__global__ __launch_bounds__(64) void zj_index_walk_emit_kernel(const u8* __restrict__ src, const u64* __restrict__ off, const u64* __restrict__ first, u32 n, u64 E,
+                                                                u64* __restrict__ size, u64* __restrict__ content, u64* __restrict__ valid) {
+    u64 const i = (u64)blockIdx.x * 64u + threadIdx.x;
+    if (i >= n) return;
+    u64 const lo = off[i], hi = off[i + 1];
+    valid[i] = zj_index_frames_emit(src + lo, hi > lo ? hi - lo : 0, first, i, E, size, content);
+}
+size_t zjni_index_count_frames_device(const void* d_src, const uint64_t* d_src_off, size_t n, uint64_t* d_piece_first, void* stream) {
+    DevState* d = cur_state();
+    if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (n > 0xFFFFFFFFull) return ZJNI_ERR(72);
+    if (!d_piece_first || (n && !d_src_off)) return ZJNI_ERR(42);
+    hipStream_t const st = (hipStream_t)stream;
+    BatchOrder order(d, stream);
+    if (n == 0) return hipMemsetAsync(d_piece_first, 0, 8, st) == hipSuccess ? 0 : ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (!frames_state(d)) return ZJNI_ERR(64);
+    size_t const r = frames_room(d, zj_up16(n * 8) + 16, 0, st);           // the counts, until the scan behind them has run (stream order)
+    if (r != 0) return r;
+    u64* const cnt = (u64*)d->framesBuf;
+    hipLaunchKernelGGL(zj_index_walk_count_kernel, dim3((u32)((n + 63) / 64)), dim3(64), 0, st, (const u8*)d_src, (const u64*)d_src_off, cnt, (u32)n);
+    hipLaunchKernelGGL(zj_pack_offsets_kernel, dim3(1), dim3(1024), 0, st, (const u64*)cnt, (u64*)d_piece_first, (u32)n);
+    return hipGetLastError() == hipSuccess ? 0 : ZJNI_ERR(ZJNI_ERROR_no_device);
+}
+size_t zjni_index_from_frames_device(const void* d_src, const uint64_t* d_src_off, size_t n, const uint64_t* d_piece_first, size_t E, void* d_index,
+                                     uint64_t* d_piece_size, uint64_t* d_piece_content, void* stream) {
+    DevState* d = cur_state();
+    if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (n > 0xFFFFFFFFull || E > 0xFFFFFFFFull) return ZJNI_ERR(72);
+    if (!d_index || !d_piece_first || (n && !d_src_off)) return ZJNI_ERR(42);
+    hipStream_t const st = (hipStream_t)stream;
+    BatchOrder order(d, stream);
+    u64* const idx = (u64*)d_index;
+    u64* const valid = idx + n + 1; u64* const C = idx + 2 * n + 1; u64* const U = C + E + 1;
+    // the two arrays the walk writes and the scan reads: the caller's, or library scratch until the scan has run (stream order)
+    size_t const arr = zj_up16(E * 8) + 16;
+    u64* size = (u64*)d_piece_size; u64* content = (u64*)d_piece_content;
+    if (E && (!size || !content)) {
+        if (!frames_state(d)) return ZJNI_ERR(64);
+        size_t const r = frames_room(d, 2 * arr, 0, st);
+        if (r != 0) return r;
+        if (!size) size = (u64*)d->framesBuf;
+        if (!content) content = (u64*)(d->framesBuf + arr);
+    }
+    if (hipMemcpyAsync(idx, d_piece_first, (n + 1) * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    // (an entry no buffer owns, which only a false d_piece_first leaves, counts nothing)
+    if (E && (hipMemsetAsync(size, 0, E * 8, st) != hipSuccess || hipMemsetAsync(content, 0, E * 8, st) != hipSuccess)) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (n) hipLaunchKernelGGL(zj_index_walk_emit_kernel, dim3((u32)((n + 63) / 64)), dim3(64), 0, st, (const u8*)d_src, (const u64*)d_src_off, (const u64*)d_piece_first, (u32)n, (u64)E,
+                              size, content, valid);
+    hipLaunchKernelGGL(zj_index_scan_kernel, dim3(2), dim3(ZJ_INDEX_SCAN_WG), 0, st, (const u64*)size, (const u64*)content, (u64)E, C, U);
+    return hipGetLastError() == hipSuccess ? 0 : ZJNI_ERR(ZJNI_ERROR_no_device);
+}
+
 // per request: [rec R][ireq R][bad R][q 5 x R][scan 5 x (R + 1)][totals 5] — the range layer's, with the request's place in the index and its mark beside the record
 // one lane per request: rules 1-4 by bisection
 __global__ __launch_bounds__(64) void zj_index_request_kernel(const u64* __restrict__ idx, u64 n, u64 E, const u64* __restrict__ off, const u64* __restrict__ req, const u64* __restrict__ dstOff,
@@ -4579,6 +4642,17 @@ size_t zjni_decompress_index_range(void* dst, size_t dstCap, const void* src, si
     if (hipMemcpyAsync(sl->hPinned + oDst, sl->dStage + oDst, res, hipMemcpyDeviceToHost, hst) != hipSuccess || hipStreamSynchronize(hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
     memcpy(dst, sl->hPinned + oDst, res);
     return res;
+}
+
+// The walk on the host, no device: the arrays zjni_decompress_index_range takes, from the bytes alone, by the function both device walks run.
+size_t zjni_index_from_frames(const void* src, size_t srcSize, uint64_t* pieceSize, uint64_t* pieceContent, size_t capacity, size_t* nPieces) {
+    if (nPieces) *nPieces = 0;
+    if ((srcSize && !src) || (capacity && (!pieceSize || !pieceContent))) return ZJNI_ERR(72);
+    u64 entries = 0, wrote = 0;
+    u32 const verdict = zj_index_walk((const u8*)src, (u64)srcSize, (u64)capacity, (u64*)pieceSize, (u64*)pieceContent, &entries, &wrote);
+    if (verdict) return ZJNI_ERR(verdict);
+    if (nPieces) *nPieces = (size_t)entries;
+    return entries > capacity ? ZJNI_ERR(70) : 0;
 }
 
 }  // extern "C"
