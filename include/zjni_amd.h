@@ -254,6 +254,7 @@ size_t zjni_decompress_frames_range(void* dst, size_t dstCapacity, const void* s
 #define ZJNI_FRAME_CHECKSUM       1
 #define ZJNI_FRAME_NO_CONTENTSIZE 2
 #define ZJNI_FRAME_NO_DICTID      4
+#define ZJNI_SEQ_REPCODES         8   /* the sequence entries below only: ZSTD_c_searchForExternalRepcodes = enable */
 size_t zjni_compress_batch_device_advanced(const void* d_src, const uint64_t* d_src_off,
                                            void* d_dst, const uint64_t* d_dst_off,
                                            uint64_t* d_result, size_t n, int level, int checksum, int hashLog, int chainLog, void* stream);
@@ -634,6 +635,38 @@ int zjni_last_decode_lists2(unsigned* out5);
  * One launch for the frames to 64 KiB, one for the wider ones.  d_result[i] as zjni_compress_batch_device2.  Synchronous. */
 size_t zjni_test_compress_records_batch_device(const void* d_src, const uint64_t* d_src_off, const uint32_t* h_rec, const uint64_t* h_rec_off, const uint32_t* h_meta,
                                                void* d_dst, const uint64_t* d_dst_off, uint64_t* d_result, size_t n, int level, int checksum, int stagedLds, int grid, void* stream);
+/* ---- frames from the CALLER's sequences: ZSTD_compressSequences (N/compress/zstd_compress.c:7063-7110) for batches ----
+ * The seam inside the library made public: a match finder writes sequences, the entropy stage turns them into blocks.  These entries take the sequences from
+ * outside — a parse of the caller's own, a hardware match finder, a transcoder — and run only the entropy stage, at its speed.  Frame i is, byte for byte, what
+ * the reference writes for ZSTD_compressSequences(cctx, dst, cap, seqs, nSeqs, src, srcSize) on a fresh CCtx with ZSTD_c_compressionLevel = level,
+ * ZSTD_c_checksumFlag = flags & ZJNI_FRAME_CHECKSUM, ZSTD_c_blockDelimiters = ZSTD_sf_explicitBlockDelimiters, ZSTD_c_validateSequences = 1 and
+ * ZSTD_c_searchForExternalRepcodes = enable with ZJNI_SEQ_REPCODES, disable without; any other flag bit: 42.
+ *   - the caller cuts the blocks: a delimiter is a sequence with offset == 0 and matchLength == 0 whose litLength counts the block's last literals.  A block of
+ *     less than 7 bytes is stored raw; a block that ends where the source ends is the last one and whatever follows it in the array is ignored; `rep` is ignored.
+ *   - ZSTD_error_externalSequences_invalid (107) in the frame's slot, and only there: offset == 0 with a match length; no delimiter before the array ends; a block
+ *     above 128 KiB or blocks that sum past the source; blocks that end before the source does; a match shorter than 4 (3 where the level's minMatch is 3); an
+ *     offset beyond the bytes that precede the END of its match.  That last bound is the reference's: an offset may reach up to matchLength bytes in front of the
+ *     source, the reference then writes a frame no decoder accepts, and so do these entries.  It is safe because the entropy stage never dereferences a match,
+ *     only literals: nothing is read outside the sequence array and the source whatever the array holds.  (Lengths above 128 KiB answer 107 here; the reference
+ *     adds litLength + matchLength in 32 bits first and is not defined on arrays that wrap.)
+ *   - levels and sizes: those zjni_compress_batch_device serves (1-3 to ZJNI_FRAME_MAX inside the level's window, 4 to 128 KiB, 5-8 as there, every negative
+ *     level), 201 otherwise; 0 means 3.  Where the level's row for the size is lazy or lazy2 (level 5 to 16 KiB, levels 6-8) a frame is served while its first block
+ *     of 7 bytes or more is its last, a second one answers 201: those strategies weigh the previous block's sequence tables, which the entropy stage does not carry.
+ *   - destinations as zjni_compress_batch_device2: every capacity gives the reference's size, bytes or dstSize_tooSmall (18 bytes for the header first).
+ *   - no dictionary, no ZSTD_sf_noBlockDelimiters.
+ * d_seq_off[n + 1] counts SEQUENCES (frame i's are d_seqs[d_seq_off[i] .. d_seq_off[i + 1])).  Scratch: 20 bytes per sequence of the call from the library's
+ * pool (zjni_set_scratch_limit applies; 64 when the call's records alone exceed it), sized from d_seq_off[n], which is read back once — the entry's one host wait;
+ * everything else is enqueued on `stream`. */
+typedef struct zjni_sequence { uint32_t offset, litLength, matchLength, rep; } zjni_sequence;      /* == ZSTD_Sequence, 16 bytes */
+size_t zjni_sequenceBound(size_t srcSize);                                                         /* == ZSTD_sequenceBound: sequences a source of this size can need, delimiters included */
+size_t zjni_compress_sequences_batch_device(const void* d_src, const uint64_t* d_src_off, const zjni_sequence* d_seqs, const uint64_t* d_seq_off,
+                                            void* d_dst, const uint64_t* d_dst_off, uint64_t* d_result, size_t n, int level, int flags, void* stream);
+/* The same with host arrays (as zjni_compress_batch2, plus seqs[i] / nSeqs[i]); staged through a device buffer of the call's own.  Synchronous. */
+size_t zjni_compress_sequences_batch(const void* const* src, const size_t* srcSize, const zjni_sequence* const* seqs, const size_t* nSeqs,
+                                     void* const* dst, const size_t* dstCapacity, size_t* result, size_t n, int level, int flags);
+size_t zjni_compress_sequences(void* dst, size_t dstCapacity, const zjni_sequence* seqs, size_t nSeqs, const void* src, size_t srcSize, int level, int flags);
+/* Tests: at most `grid` workgroups for the two launches of the sequence entries (1: one workgroup meets every frame in turn); 0 restores the default.  Returns the previous value. */
+int zjni_debug_sequences_grid(int grid);
 /* Name of the kernel a route's match-finder time (zjni_last_timing out[0]) belongs to. */
 const char* zjni_route_kernel(int route);
 /* The source revision the library was built from ("unknown" when the build had no git): profiles and PMC passes are stamped with it. */

@@ -283,8 +283,40 @@ def lib():
     if hasattr(L, "zjni_test_compress_records_batch_device"):      # test entry: the entropy stage on the caller's records
         L.zjni_test_compress_records_batch_device.restype = sz
         L.zjni_test_compress_records_batch_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, sz, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+    L.zjni_sequenceBound.restype = sz                               # frames from the caller's sequences (ZSTD_compressSequences)
+    L.zjni_sequenceBound.argtypes = [sz]
+    L.zjni_compress_sequences_batch_device.restype = sz
+    L.zjni_compress_sequences_batch_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, sz, C.c_int, C.c_int, vp]
+    L.zjni_compress_sequences_batch.restype = sz
+    L.zjni_compress_sequences_batch.argtypes = [C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), sz, C.c_int, C.c_int]
+    L.zjni_compress_sequences.restype = sz
+    L.zjni_compress_sequences.argtypes = [vp, sz, vp, sz, vp, sz, C.c_int, C.c_int]
+    L.zjni_debug_sequences_grid.restype = C.c_int
+    L.zjni_debug_sequences_grid.argtypes = [C.c_int]
     _lib = L
     return L
+
+
+SEQ_REPCODES = 8       # ZJNI_SEQ_REPCODES, beside the checksum bit (1) in the flag word of the sequence entries
+
+
+def sequence_bound(n):
+    """zjni_sequenceBound == ZSTD_sequenceBound: the sequences (delimiters included) a source of n bytes can need."""
+    return lib().zjni_sequenceBound(n)
+
+
+def compress_sequences(data, seqs, level, flags=0):
+    """zjni_compress_sequences: one host buffer and its (k, 4) uint32 array of ZSTD_Sequence rows {offset, litLength, matchLength, rep} with explicit block
+    delimiters -> the frame ZSTD_compressSequences writes (flags: 1 checksum, SEQ_REPCODES).  Raises ZstdException with the reference's code otherwise."""
+    import numpy as np
+    arr = np.ascontiguousarray(np.asarray(seqs, dtype=np.uint32).reshape(-1, 4))
+    buf = bytes(data)
+    cap = lib().zjni_compressBound(len(buf)) + 64 + 3 * (len(arr) + 1)            # every delimiter may add a block header
+    dst = C.create_string_buffer(cap)
+    r = lib().zjni_compress_sequences(dst, cap, arr.ctypes.data if len(arr) else None, len(arr), buf, len(buf), level, flags)
+    if lib().zjni_isError(r):
+        raise ZstdException(r)
+    return dst.raw[:r]
 
 
 EXPORTS = ("zjni_version", "zjni_device_count", "zjni_init", "zjni_shutdown", "zjni_isError",
@@ -313,7 +345,8 @@ EXPORTS = ("zjni_version", "zjni_device_count", "zjni_init", "zjni_shutdown", "z
            "zjni_index_bytes", "zjni_index_from_sizes_device", "zjni_index_from_pieces_device", "zjni_decompress_index_range_batch_device",
            "zjni_last_index_range", "zjni_decompress_index_range",
            "zjni_index_count_frames_device", "zjni_index_from_frames_device", "zjni_index_from_frames",
-           "zjni_test_compress_records_batch_device")
+           "zjni_test_compress_records_batch_device",
+           "zjni_sequenceBound", "zjni_compress_sequences_batch_device", "zjni_compress_sequences_batch", "zjni_compress_sequences", "zjni_debug_sequences_grid")
 
 
 def decompress_index_range(src, lo, length, piece_size, piece_content, dictionary=None, capacity=None):

@@ -434,6 +434,36 @@ def pack(results, dst_blob, dst_off, out=None, out_off=None):
     return out, out_off
 
 
+def compress_sequences(src, src_off, seqs, seq_off, level, flags=0, dst=None, dst_off=None, results=None, _grid=0):
+    """Enqueue zjni_compress_sequences_batch_device on the current stream: frames from the CALLER's sequences (ZSTD_compressSequences with explicit
+    block delimiters).  src uint8 blob and src_off int64[n + 1] as everywhere; seqs an int32 / uint32 [k, 4] device tensor of ZSTD_Sequence rows
+    {offset, litLength, matchLength, rep}, seq_off int64[n + 1] counting rows.  flags: 1 checksum, 8 ZJNI_SEQ_REPCODES.  Without dst / dst_off the
+    destinations are sized here (compress bound plus a block header per sequence row, which reads src_off and seq_off back).  Returns
+    (dst, dst_off, results int64[n]): the frame's size, or a negative ZSTD / ZJNI error code (107: the frame's sequences are invalid).
+    _grid: tests only, at most that many workgroups."""
+    n = src_off.numel() - 1
+    dev = src.device
+    if seqs.element_size() != 4 or not seqs.is_contiguous():
+        raise ValueError("compress_sequences: seqs must be a contiguous tensor of 32-bit rows")
+    if dst is None:
+        so, qo = src_off.cpu().tolist(), seq_off.cpu().tolist()
+        caps = [0]
+        for i in range(n):
+            caps.append(caps[-1] + lib().zjni_compressBound(max(so[i + 1] - so[i], 0)) + 64 + 3 * (max(qo[i + 1] - qo[i], 0) + 1))
+        dst = torch.empty(max(caps[-1], 1), dtype=torch.uint8, device=dev)
+        dst_off = torch.tensor(caps, dtype=torch.int64, device=dev)
+    if results is None:
+        results = torch.empty(max(n, 1), dtype=torch.int64, device=dev)[:n]
+    prev = lib().zjni_debug_sequences_grid(_grid) if _grid else 0
+    try:
+        _check(lib().zjni_compress_sequences_batch_device(src.data_ptr(), src_off.data_ptr(), seqs.data_ptr(), seq_off.data_ptr(), dst.data_ptr(), dst_off.data_ptr(),
+                                                          results.data_ptr(), n, level, flags, _stream_ptr()))
+    finally:
+        if _grid:
+            lib().zjni_debug_sequences_grid(prev)
+    return dst, dst_off, results
+
+
 def _test_compress_records(datas, records, level, checksum=False, staged_lds=False, grid=0):
     """TEST ENTRY (zjni_test_compress_records_batch_device): the entropy stage on sequences the caller wrote.  datas: the sources (bytes, one block each);
     records[i] = (flat [ll, ml, offBase, pos] * nbSeq, litSize, lastLL) for source i.  staged_lds: the dynamic LDS of the dictionary pipeline's entropy launch

@@ -1520,6 +1520,11 @@ template <> struct ZEEntOf<u32> { typedef ZEEnt32 E; };
 // Sequences found ahead of time by the lane-per-frame match-finder kernel (zj_enc_match_kernel)
 struct ZEPre { ZESeq* seqs; const u32* litOff; const u32* meta; u32 copyMode = 0; };   // meta = {nbSeq, litSize, lastLL}; copyMode: the records come from the dictionary copy-mode search (zj_cdict.h)
 
+// Which test makes a block of one repeated byte an RLE block: ZSTD_compressBlock_internal's (the compressed size, zstd_compress.c:4422-4447) or, for groups
+// that say so, ZSTD_compressSequences_internal's (ZSTD_maybeRLE on the sequence store, :7012-7020) — a compile-time property of the group, so the sequence
+// entries get an instantiation of their own (zj_sequences.h) and every other kernel's code stays what it was
+template <class G> struct ZEExtSeq { static constexpr bool v = false; };
+
 // zj_match_wavex.h (included at the end of this file): the wave-per-frame parse of one level-3 block of a multi-block frame
 ZJ_DEV u32 zx_block_dfast_wave(u8* lds, ZEOut& o, const u8* base, u32 frameSize, u32 start, u32 end, u32 hBitsL, u32 hBitsS, u32 mls,
                                u32* hashLong, u32* hashSmall, const u32* repIn, u32* repOut, bool carry);
@@ -2137,7 +2142,7 @@ ZJ_DEV u64 ze_compress_t(const G& g, ZEncShared& sh, u8* lds, const u8* src0, u3
             compressed = false;
         }
         u32 type = compressed ? 2u : 0u;
-        if (srcSize >= 7 && !ba->isFirst && (compressed ? cSize : 0u) < 25u) {
+        if (srcSize >= 7 && !ba->isFirst && (ZEExtSeq<G>::v ? (ZJ_UNI(sh.nbSeq) < 4u && ZJ_UNI(sh.litSize) < 10u) : (compressed ? cSize : 0u) < 25u)) {
             GRP_SERIAL(g) { sh.tmp[0] = 1; }
             g.sync();
             u32 const b0 = src0[0];

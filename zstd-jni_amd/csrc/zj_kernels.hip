@@ -34,6 +34,7 @@
 #include "zj_frames.h"
 #include "zj_frames_range.h"
 #include "zj_index.h"
+#include "zj_sequences.h"
 
 #define ZJNI_ERR(code) ((size_t)0 - (size_t)(code))
 
@@ -3715,6 +3716,153 @@ static size_t frames_read_total(DevState* d, const u64* d_total, hipStream_t st,
     return 0;
 }
 static inline size_t zj_up16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// ---- frames from the caller's sequences: ZSTD_compressSequences for batches (zj_sequences.h) ----
+// Two launches on `stream`, nothing else: the conversion (a wave per frame from a work counter) and the frame loop (a workgroup per frame from a second one).
+// Records, literal offsets and block entries live in framesBuf — 20 bytes per sequence of the call and 4 per frame, counted as scratch (zjni_set_scratch_limit;
+// a call whose records alone exceed the limit answers 64) — whose size is the one thing the host has to know: d_seq_off[n], eight bytes read back once through
+// pinned memory, the entry's only host wait.  A frame's slice of the array is checked against that total on the device before anything of it is read.
+__global__ __launch_bounds__(64) void zj_seq_convert_kernel(const u64* __restrict__ srcOff, const ZSSeq* __restrict__ seqs, const u64* __restrict__ seqOff, u64 total,
+                                                            ZESeq* __restrict__ rec, u32* __restrict__ lit, u32* __restrict__ nBlk, u32 n, u32 level, u32 flags, u32* workCounter) {
+    GrpSeq<64> g;
+    for (;;) {
+        u32 const i = zj_next_index(workCounter);
+        if (i >= n) break;
+        u64 const q0 = zj_uni64(seqOff[i]), q1 = zj_uni64(seqOff[i + 1]), s0 = zj_uni64(srcOff[i]), s1 = zj_uni64(srcOff[i + 1]);
+        if (q0 > q1 || q1 > total || q1 - q0 > 0x7FFFFFFFull || s1 < s0) { if (threadIdx.x == 0) nBlk[i] = ZS_NO_FRAME; continue; }
+        u64 const size64 = s1 - s0;
+        u32 const srcSize = size64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)size64;
+        ZEParams const p = ze_params_of(level, srcSize);
+        if (p.strategy == 0u || srcSize > ZE_MULTI_MAX) { if (threadIdx.x == 0) nBlk[i] = 0u; continue; }       // the frame loop answers 201 before it looks at a slot
+        zs_convert(g, seqs + q0, (u32)(q1 - q0), srcSize, zs_ml_min(p), zs_max_nbseq(p, srcSize), (flags & ZS_FLAG_REPCODES) != 0u, rec + q0 + i, lit + q0 + i, nBlk + i);
+    }
+}
+// (the register budget of zj_encode_kernel, whose stage this is: three waves per SIMD)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 8))) void zj_encode_sequences_kernel(const u8* __restrict__ src, const u64* __restrict__ srcOff, const u64* __restrict__ seqOff,
+                                                                 u8* __restrict__ dst, const u64* __restrict__ dstOff, u64* __restrict__ result, u32 n, u32 level, u32 flags,
+                                                                 ZESeq* rec, const u32* lit, const u32* nBlk, u32* workCounter, u8* scratch, u32 ldsBytes) {
+    __shared__ ZEncShared sh;
+    __shared__ ZSState st;
+    ZjProf pf; pf.start(nullptr);
+    GrpSeq<64> g;
+    if (threadIdx.x == 0) { sh.dictLoaded = 0; sh.ctDict[0] = 0; sh.ctDict[1] = 0; sh.ctDict[2] = 0; }
+    __syncthreads();
+    u8* const ws = scratch + (size_t)blockIdx.x * ZE_SCRATCH_BYTES;
+    for (;;) {
+        u32 const i = zj_next_index(workCounter);
+        if (i >= n) break;
+        u64 const s0 = zj_uni64(srcOff[i]), s1 = zj_uni64(srcOff[i + 1]), d0 = zj_uni64(dstOff[i]), d1 = zj_uni64(dstOff[i + 1]);
+        u32 const nb = ZJ_UNI(nBlk[i]);
+        u64 const q0 = nb == ZS_NO_FRAME ? 0 : zj_uni64(seqOff[i]);
+        u64 const cap = d1 - d0;
+        u64 r;
+        if (s1 < s0 || d1 < d0) r = ZJ_ERR64(ZJ_E_SRCSIZE_WRONG);
+        else if (s1 - s0 > ZE_MULTI_MAX) r = ZJ_ERR64(201);
+        else r = zs_compress_frame(g, sh, st, zj_dyn_lds, src + s0, (u32)(s1 - s0), dst + d0, (u32)(cap > 0xFFFFFFFFull ? 0xFFFFFFFFull : cap), level, flags,
+                                   rec + q0 + i, lit + q0 + i, nb, ws, pf, ldsBytes);
+        if (threadIdx.x == 0) result[i] = r;
+        __syncthreads();
+    }
+}
+static std::atomic<int> g_seq_grid(0);           // zjni_debug_sequences_grid
+int zjni_debug_sequences_grid(int grid) { return g_seq_grid.exchange(grid < 0 ? 0 : grid); }
+size_t zjni_sequenceBound(size_t srcSize) { return (size_t)zs_sequence_bound(srcSize); }
+size_t zjni_compress_sequences_batch_device(const void* d_src, const uint64_t* d_src_off, const zjni_sequence* d_seqs, const uint64_t* d_seq_off,
+                                            void* d_dst, const uint64_t* d_dst_off, uint64_t* d_result, size_t n, int level, int flags, void* stream) {
+    static_assert(sizeof(zjni_sequence) == 16 && sizeof(ZSSeq) == 16 && ZJNI_SEQ_REPCODES == ZS_FLAG_REPCODES && ZJNI_FRAME_CHECKSUM == ZE_FLAG_CHECKSUM, "zjni_sequence is ZSTD_Sequence");
+    if (flags & ~(ZJNI_FRAME_CHECKSUM | ZJNI_SEQ_REPCODES)) return ZJNI_ERR(42);
+    if (level == 0) level = 3;                    // ZSTD_CLEVEL_DEFAULT
+    if (!zj_level_served(level)) return ZJNI_ERR(42);
+    if (n == 0) return 0;
+    if (n > 0x7FFFFFFFull) return ZJNI_ERR(72);
+    if (!d_src_off || !d_seq_off || !d_dst_off || !d_result) return ZJNI_ERR(42);
+    DevState* d = cur_state();
+    if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    BatchOrder order(d, stream);
+    hipStream_t st = (hipStream_t)stream;
+    if (!frames_state(d)) return ZJNI_ERR(64);
+    u64 total = 0;
+    {   size_t const e = frames_read_total(d, d_seq_off + n, st, &total); if (e) return e; }
+    if (total > ((u64)1 << 40)) return ZJNI_ERR(64);
+    if (total && !d_seqs) return ZJNI_ERR(42);
+    size_t const slots = (size_t)total + n;
+    size_t const offNblk = 64, offLit = offNblk + zj_up16(n * 4), offRec = offLit + zj_up16(slots * 4), need = offRec + slots * 16;
+    {   size_t const e = frames_room(d, need, 0, st); if (e) return e; }
+    u32* const ctr = (u32*)d->framesBuf;
+    if (hipMemsetAsync(ctr, 0, 64, st) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    static std::mutex gridMu; static std::map<int, int> gridOf;                      // resident workgroups of the frame loop per device, asked for once
+    int grid;
+    {   std::lock_guard<std::mutex> lk(gridMu);
+        auto it = gridOf.find(d->ordinal);
+        if (it == gridOf.end()) {
+            int perCU = 0;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, zj_encode_sequences_kernel, 64, sizeof(ZEEntropy)) != hipSuccess || perCU < 1) { (void)hipGetLastError(); perCU = 1; }
+            int gmax = d->numCU * perCU;
+            if (gmax > d->encGrid) gmax = d->encGrid;                                // a scratch slot per workgroup
+            it = gridOf.emplace(d->ordinal, gmax).first;
+        }
+        grid = it->second; }
+    int const want = g_seq_grid.load();
+    if (want > 0 && want < grid) grid = want;
+    if ((size_t)grid > n) grid = (int)n;
+    u32 const lw = zs_level_word(level);
+    ZESeq* const rec = (ZESeq*)(d->framesBuf + offRec); u32* const lit = (u32*)(d->framesBuf + offLit); u32* const nBlk = (u32*)(d->framesBuf + offNblk);
+    size_t convGrid = (size_t)d->numCU * 8; if (convGrid > n) convGrid = n; if (want > 0 && (size_t)want < convGrid) convGrid = (size_t)want;
+    hipLaunchKernelGGL(zj_seq_convert_kernel, dim3((u32)convGrid), dim3(64), 0, st, (const u64*)d_src_off, (const ZSSeq*)d_seqs, (const u64*)d_seq_off, total, rec, lit, nBlk, (u32)n, lw, (u32)flags, ctr);
+    if (hipGetLastError() != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    hipLaunchKernelGGL(zj_encode_sequences_kernel, dim3((u32)grid), dim3(64), sizeof(ZEEntropy), st, (const u8*)d_src, (const u64*)d_src_off, (const u64*)d_seq_off, (u8*)d_dst,
+                       (const u64*)d_dst_off, (u64*)d_result, (u32)n, lw, (u32)flags, rec, (const u32*)lit, (const u32*)nBlk, ctr + 1, d->encScratch, (u32)sizeof(ZEEntropy));
+    return hipGetLastError() == hipSuccess ? 0 : ZJNI_ERR(ZJNI_ERROR_no_device);
+}
+// Host arrays: sources, sequence arrays and destinations go through one device buffer of the call's own (packed on the host, one copy each way).  Synchronous.
+size_t zjni_compress_sequences_batch(const void* const* src, const size_t* srcSize, const zjni_sequence* const* seqs, const size_t* nSeqs,
+                                     void* const* dst, const size_t* dstCap, size_t* result, size_t n, int level, int flags) {
+    if (flags & ~(ZJNI_FRAME_CHECKSUM | ZJNI_SEQ_REPCODES)) return ZJNI_ERR(42);
+    if (level == 0) level = 3;
+    if (!zj_level_served(level)) return ZJNI_ERR(42);
+    if (n == 0) return 0;
+    if (n > 0x7FFFFFFFull) return ZJNI_ERR(72);
+    if (!src || !srcSize || !seqs || !nSeqs || !dst || !dstCap || !result) return ZJNI_ERR(42);
+    std::vector<u64> off(3 * (n + 1));
+    u64* const so = off.data(); u64* const qo = so + n + 1; u64* const dof = qo + n + 1;
+    so[0] = qo[0] = dof[0] = 0;
+    for (size_t i = 0; i < n; i++) {
+        if ((srcSize[i] && !src[i]) || (nSeqs[i] && !seqs[i]) || (dstCap[i] && !dst[i])) return ZJNI_ERR(72);
+        if (srcSize[i] > ((size_t)1 << 40) || nSeqs[i] > ((size_t)1 << 36) || dstCap[i] > ((size_t)1 << 40)) return ZJNI_ERR(64);
+        so[i + 1] = so[i] + srcSize[i]; qo[i + 1] = qo[i] + nSeqs[i]; dof[i + 1] = dof[i] + dstCap[i];
+    }
+    if (!cur_state()) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    size_t const aSrc = 0, aSeq = zj_up16(so[n]), aOff = aSeq + zj_up16(qo[n] * 16), inBytes = aOff + off.size() * 8;
+    size_t const aRes = zj_up16(inBytes), aDst = aRes + zj_up16(n * 8), all = aDst + dof[n];
+    std::vector<u8> image(inBytes);
+    for (size_t i = 0; i < n; i++) {
+        if (srcSize[i]) memcpy(image.data() + aSrc + so[i], src[i], srcSize[i]);
+        if (nSeqs[i]) memcpy(image.data() + aSeq + qo[i] * 16, seqs[i], nSeqs[i] * 16);
+    }
+    memcpy(image.data() + aOff, off.data(), off.size() * 8);
+    u8* buf = nullptr;
+    if (hipMalloc(&buf, all ? all : 1) != hipSuccess) { (void)hipGetLastError(); return ZJNI_ERR(64); }
+    size_t r = 0;
+    if (hipMemcpy(buf, image.data(), inBytes, hipMemcpyHostToDevice) != hipSuccess) r = ZJNI_ERR(ZJNI_ERROR_no_device);
+    const u64* const dOff = (const u64*)(buf + aOff);
+    if (r == 0) r = zjni_compress_sequences_batch_device(buf + aSrc, dOff, (const zjni_sequence*)(buf + aSeq), dOff + n + 1, buf + aDst, dOff + 2 * (n + 1), (uint64_t*)(buf + aRes), n, level, flags, nullptr);
+    std::vector<u8> back(all - aRes);
+    if (r == 0 && (hipStreamSynchronize(nullptr) != hipSuccess || hipMemcpy(back.data(), buf + aRes, all - aRes, hipMemcpyDeviceToHost) != hipSuccess)) r = ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (hipDeviceSynchronize() != hipSuccess && r == 0) r = ZJNI_ERR(ZJNI_ERROR_no_device);       // nothing may still use `buf`
+    (void)hipFree(buf);
+    if (r) return r;
+    const u64* const res = (const u64*)back.data();
+    for (size_t i = 0; i < n; i++) {
+        result[i] = (size_t)res[i];
+        if (!zjni_isError((size_t)res[i]) && res[i] <= dstCap[i] && res[i]) memcpy(dst[i], back.data() + (aDst - aRes) + dof[i], (size_t)res[i]);
+    }
+    return 0;
+}
+size_t zjni_compress_sequences(void* dst, size_t dstCapacity, const zjni_sequence* seqs, size_t nSeqs, const void* src, size_t srcSize, int level, int flags) {
+    size_t res = 0; const void* s = src; void* dd = dst; const zjni_sequence* q = seqs;
+    size_t const r = zjni_compress_sequences_batch(&s, &srcSize, &q, &nSeqs, &dd, &dstCapacity, &res, 1, level, flags);
+    return zjni_isError(r) ? r : res;
+}
 
 // ---- frame-parallel decompress ----
 // first walk, one lane per buffer as zj_inspect_kernel walks: cnt[i] = entries of buffer i
