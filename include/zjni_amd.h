@@ -667,6 +667,35 @@ size_t zjni_compress_sequences_batch(const void* const* src, const size_t* srcSi
 size_t zjni_compress_sequences(void* dst, size_t dstCapacity, const zjni_sequence* seqs, size_t nSeqs, const void* src, size_t srcSize, int level, int flags);
 /* Tests: at most `grid` workgroups for the two launches of the sequence entries (1: one workgroup meets every frame in turn); 0 restores the default.  Returns the previous value. */
 int zjni_debug_sequences_grid(int grid);
+/* ---- the matchers' sequences OUT: ZSTD_generateSequences (N/compress/zstd_compress.c:3520-3553, ZSTD_copyBlockSequences :3429-3512) for batches ----
+ * The first half of the same seam: the match finders' parse of a source as ZSTD_Sequence[], for a caller who wants the parse alone — a transcoder, a match
+ * statistics pass, a second entropy coder, a dictionary trainer — or who feeds it back to zjni_compress_sequences_*.  Frame i's slots hold what the reference
+ * writes for ZSTD_generateSequences(cctx, out, cap, src, srcSize) on a fresh CCtx with only ZSTD_c_compressionLevel = level set:
+ *   - per block its sequences {offset, litLength, matchLength, rep} — `offset` the RAW offset, `rep` 0 or the repcode number 1-3 the parser used — and one
+ *     delimiter {0, lastLiterals, 0, 0} behind them (the reference leaves a delimiter's `rep` as the caller's memory held it; these entries write 0).  Lengths
+ *     of 65 536 and more come out as they are.  A block is min(128 KiB, what is left) and every block confirms its repcodes (collecting mode, :4408-4411).
+ *   - d_result[i]: the entries written, delimiters included, or an error code in the frame's slot, and only there: ZSTD_error_sequenceProducer_failed (106) for a
+ *     source whose last block has fewer than 7 bytes (1-6 bytes, k x 128 KiB + 1 .. 6), as the reference; an empty source answers 0; dstSize_tooSmall (70) when
+ *     a block's sequences plus its delimiter do not fit what is left of the slots (checked per block, before the block is written); 201 for a (level, size)
+ *     zjni_compress_batch_device refuses.  On an error the slots' content is undefined; nothing is written outside them.  zjni_sequenceBound(srcSize) slots are always enough.
+ *   - levels and sizes: those zjni_compress_batch_device serves without a dictionary (1-3 and every negative level to ZJNI_FRAME_MAX inside the level's window,
+ *     multi-block frames included; 4-8 to 128 KiB); 0 means 3, and level 3 parses with the reference's own table sizes.  Any `flags` bit: 42, none is defined yet.
+ *   - fed to zjni_compress_sequences_* the result gives a frame that decodes to the source; it is NOT ZSTD_compress2's frame (the reference's is not either).
+ * d_seq_off[n + 1] counts SLOTS: frame i owns d_seqs[d_seq_off[i] .. d_seq_off[i + 1]).  Everything is enqueued on `stream`; the host waits only where scratch has
+ * to grow (64 bytes of counters, once).  Every frame takes one wave of one kernel (parse, then export); the lane match kernels of large batches are not used yet. */
+size_t zjni_generate_sequences_batch_device(const void* d_src, const uint64_t* d_src_off,
+        zjni_sequence* d_seqs, const uint64_t* d_seq_off /* [n + 1]: frame i owns slots d_seq_off[i] .. d_seq_off[i + 1] */,
+        uint64_t* d_result, size_t n, int level, int flags, void* stream);
+/* The same with host arrays; staged through a device buffer of the call's own.  Synchronous. */
+size_t zjni_generate_sequences_batch(const void* const* src, const size_t* srcSize, zjni_sequence* const* seqs,
+        const size_t* seqCapacity, size_t* result, size_t n, int level, int flags);
+size_t zjni_generate_sequences(zjni_sequence* seqs, size_t seqCapacity, const void* src, size_t srcSize, int level);
+size_t zjni_mergeBlockDelimiters(zjni_sequence* seqs, size_t nSeqs);                         /* == ZSTD_mergeBlockDelimiters, host code */
+/* The last generate call: out4[0] frames sent through a lane route (none yet: always 0), out4[1] through the wave route, out4[2] frames that answered an error code,
+ * out4[3] 0.  Waits for the device (diagnostics: benches, tests); -1 when no generate call's counters are there to read. */
+int    zjni_last_generate(unsigned out4[4]);
+/* Tests: at most `grid` workgroups for the launch of the generate entries; 0 restores the default.  Returns the previous value. */
+int    zjni_debug_generate_grid(int grid);
 /* Name of the kernel a route's match-finder time (zjni_last_timing out[0]) belongs to. */
 const char* zjni_route_kernel(int route);
 /* The source revision the library was built from ("unknown" when the build had no git): profiles and PMC passes are stamped with it. */

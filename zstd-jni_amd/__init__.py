@@ -293,6 +293,18 @@ def lib():
     L.zjni_compress_sequences.argtypes = [vp, sz, vp, sz, vp, sz, C.c_int, C.c_int]
     L.zjni_debug_sequences_grid.restype = C.c_int
     L.zjni_debug_sequences_grid.argtypes = [C.c_int]
+    L.zjni_generate_sequences_batch_device.restype = sz             # the matchers' sequences out (ZSTD_generateSequences)
+    L.zjni_generate_sequences_batch_device.argtypes = [vp, vp, vp, vp, vp, sz, C.c_int, C.c_int, vp]
+    L.zjni_generate_sequences_batch.restype = sz
+    L.zjni_generate_sequences_batch.argtypes = [C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(sz), sz, C.c_int, C.c_int]
+    L.zjni_generate_sequences.restype = sz
+    L.zjni_generate_sequences.argtypes = [vp, sz, vp, sz, C.c_int]
+    L.zjni_mergeBlockDelimiters.restype = sz
+    L.zjni_mergeBlockDelimiters.argtypes = [vp, sz]
+    L.zjni_last_generate.restype = C.c_int
+    L.zjni_last_generate.argtypes = [C.POINTER(C.c_uint)]
+    L.zjni_debug_generate_grid.restype = C.c_int
+    L.zjni_debug_generate_grid.argtypes = [C.c_int]
     _lib = L
     return L
 
@@ -317,6 +329,27 @@ def compress_sequences(data, seqs, level, flags=0):
     if lib().zjni_isError(r):
         raise ZstdException(r)
     return dst.raw[:r]
+
+
+def generate_sequences(data, level):
+    """zjni_generate_sequences: one host buffer -> its parse at `level` as a (k, 4) uint32 array of ZSTD_Sequence rows {offset, litLength, matchLength, rep}
+    with explicit block delimiters, what ZSTD_generateSequences writes.  Raises ZstdException with the reference's code otherwise (106: a last block under 7 bytes)."""
+    import numpy as np
+    buf = bytes(data)
+    cap = lib().zjni_sequenceBound(len(buf))
+    out = np.zeros((cap, 4), dtype=np.uint32)
+    r = lib().zjni_generate_sequences(out.ctypes.data, cap, buf, len(buf), level)
+    if lib().zjni_isError(r):
+        raise ZstdException(r)
+    return out[:r].copy()
+
+
+def merge_block_delimiters(seqs):
+    """zjni_mergeBlockDelimiters == ZSTD_mergeBlockDelimiters: the (k, 4) array without its delimiters, each one's literals added to the sequence behind it"""
+    import numpy as np
+    arr = np.ascontiguousarray(np.asarray(seqs, dtype=np.uint32).reshape(-1, 4)).copy()
+    n = lib().zjni_mergeBlockDelimiters(arr.ctypes.data if len(arr) else None, len(arr))
+    return arr[:n]
 
 
 EXPORTS = ("zjni_version", "zjni_device_count", "zjni_init", "zjni_shutdown", "zjni_isError",
@@ -346,7 +379,9 @@ EXPORTS = ("zjni_version", "zjni_device_count", "zjni_init", "zjni_shutdown", "z
            "zjni_last_index_range", "zjni_decompress_index_range",
            "zjni_index_count_frames_device", "zjni_index_from_frames_device", "zjni_index_from_frames",
            "zjni_test_compress_records_batch_device",
-           "zjni_sequenceBound", "zjni_compress_sequences_batch_device", "zjni_compress_sequences_batch", "zjni_compress_sequences", "zjni_debug_sequences_grid")
+           "zjni_sequenceBound", "zjni_compress_sequences_batch_device", "zjni_compress_sequences_batch", "zjni_compress_sequences", "zjni_debug_sequences_grid",
+           "zjni_generate_sequences_batch_device", "zjni_generate_sequences_batch", "zjni_generate_sequences", "zjni_mergeBlockDelimiters", "zjni_last_generate",
+           "zjni_debug_generate_grid")
 
 
 def decompress_index_range(src, lo, length, piece_size, piece_content, dictionary=None, capacity=None):

@@ -464,6 +464,44 @@ def compress_sequences(src, src_off, seqs, seq_off, level, flags=0, dst=None, ds
     return dst, dst_off, results
 
 
+def generate_sequences(src, src_off, level, seqs=None, seq_off=None, _grid=0):
+    """Enqueue zjni_generate_sequences_batch_device on the current stream: the matchers' parse of every frame as ZSTD_Sequence rows {offset, litLength,
+    matchLength, rep} with explicit block delimiters (ZSTD_generateSequences).  src uint8 blob and src_off int64[n + 1] as everywhere; seqs an int32 / uint32
+    [k, 4] device tensor of slots and seq_off int64[n + 1] counting rows — without them the slots are sized here by sequence_bound (which reads src_off back).
+    Returns (seqs, seq_off, results int64[n]): the rows written into the frame's slots, delimiters included, or a negative error code (106: a last block under
+    7 bytes; 70: the slots are too few; 201: not served).  _grid: tests only, at most that many workgroups."""
+    n = src_off.numel() - 1
+    dev = src.device
+    if seqs is None:
+        so = src_off.cpu().tolist()
+        rows = [0]
+        for i in range(n):
+            rows.append(rows[-1] + lib().zjni_sequenceBound(max(so[i + 1] - so[i], 0)))
+        seqs = torch.empty((max(rows[-1], 1), 4), dtype=torch.int32, device=dev)
+        seq_off = torch.tensor(rows, dtype=torch.int64, device=dev)
+    if seqs.element_size() != 4 or not seqs.is_contiguous():
+        raise ValueError("generate_sequences: seqs must be a contiguous tensor of 32-bit rows")
+    results = torch.empty(max(n, 1), dtype=torch.int64, device=dev)[:n]
+    prev = lib().zjni_debug_generate_grid(_grid) if _grid else 0
+    try:
+        _check(lib().zjni_generate_sequences_batch_device(src.data_ptr(), src_off.data_ptr(), seqs.data_ptr(), seq_off.data_ptr(), results.data_ptr(), n, level, 0, _stream_ptr()))
+    finally:
+        if _grid:
+            lib().zjni_debug_generate_grid(prev)
+    return seqs, seq_off, results
+
+
+def last_generate():
+    """zjni_last_generate (synchronises): {"lane": frames the last generate_sequences() sent through a lane route (none yet: 0), "wave": frames it sent
+    through the wave-per-frame kernel, "refused": frames that answered an error code}."""
+    import ctypes as C
+    out = (C.c_uint * 4)()
+    r = lib().zjni_last_generate(out)
+    if r != 0:
+        raise ZstdException(-r, "zjni_last_generate failed")
+    return dict(zip(("lane", "wave", "refused"), [int(x) for x in out[:3]]))
+
+
 def _test_compress_records(datas, records, level, checksum=False, staged_lds=False, grid=0):
     """TEST ENTRY (zjni_test_compress_records_batch_device): the entropy stage on sequences the caller wrote.  datas: the sources (bytes, one block each);
     records[i] = (flat [ll, ml, offBase, pos] * nbSeq, litSize, lastLL) for source i.  staged_lds: the dynamic LDS of the dictionary pipeline's entropy launch

@@ -35,6 +35,7 @@
 #include "zj_frames_range.h"
 #include "zj_index.h"
 #include "zj_sequences.h"
+#include "zj_generate.h"
 
 #define ZJNI_ERR(code) ((size_t)0 - (size_t)(code))
 
@@ -3864,6 +3865,115 @@ size_t zjni_compress_sequences(void* dst, size_t dstCapacity, const zjni_sequenc
     return zjni_isError(r) ? r : res;
 }
 
+// ---- the matchers' sequences out: ZSTD_generateSequences for batches (zj_generate.h) ----
+// A dispatcher of its own with one route, one launch on `stream`: zj_generate_kernel, a workgroup of one wave per frame from a work counter, parse and export
+// (zg_generate_frame) over the workgroup's tables (ensure_multi_tables) and scratch slot, the wave matcher's scoreboards in the dynamic LDS.  It takes every frame:
+// single-block and multi-block ones, levels 1-8 and the negative ones, and the frames that only have an answer (empty, refused).  The lane pipeline's scratch is not
+// touched, so what the last compress call promised about its tables still holds.  No host wait; counters (u32, 64 bytes of framesBuf): [4] work, [10] refused.
+// Not here yet: the lane match kernels in their plain launch form followed by an export kernel for large batches of small frames.
+__global__ __launch_bounds__(64, ZJ_MULTI_WAVES) void zj_generate_kernel(const u8* __restrict__ src, const u64* __restrict__ srcOff, ZSSeq* __restrict__ seqs, const u64* __restrict__ seqOff,
+                                                                          u64* __restrict__ result, u32 level, u32 count, u32* workCounter,
+                                                                          u8* scratch, u32* tables, u32* refused) {
+    __shared__ ZEncShared sh;
+    Grp<64> g;
+    u8* const ws = scratch + (size_t)blockIdx.x * ZE_SCRATCH_BYTES;
+    u32* const tb = tables + (size_t)blockIdx.x * (ZE_MULTI_TABLE_BYTES / 4u);
+    for (;;) {
+        u32 const i = zj_next_index(workCounter);
+        if (i >= count) break;
+        u64 const s0 = zj_uni64(srcOff[i]), s1 = zj_uni64(srcOff[i + 1]), q0 = zj_uni64(seqOff[i]), q1 = zj_uni64(seqOff[i + 1]);
+        u64 r;
+        if (s1 < s0 || q1 < q0) r = ZJ_ERR64(ZJ_E_SRCSIZE_WRONG);
+        else if (s1 - s0 > ZE_MULTI_MAX) r = ZJ_ERR64(201);
+        else r = zg_generate_frame(g, sh, zj_dyn_lds, src + s0, (u32)(s1 - s0), seqs + q0, q1 - q0, level, ws, tb);
+        if (threadIdx.x == 0) { result[i] = r; if (r > ZJ_ERR64(256)) atomicAdd(refused, 1u); }
+        __syncthreads();
+    }
+}
+static std::atomic<int> g_gen_grid(0);           // zjni_debug_generate_grid
+static std::atomic<const u8*> g_gen_counters(nullptr);      // where the last generate call's counters are (zjni_last_generate)
+static std::atomic<u32> g_gen_frames(0);                    // ... and how many frames it had
+int zjni_debug_generate_grid(int grid) { return g_gen_grid.exchange(grid < 0 ? 0 : grid); }
+int zjni_last_generate(unsigned out4[4]) {
+    DevState* d = cur_state();
+    if (!d || !out4) return -(int)ZJNI_ERROR_no_device;
+    u32 h[16];
+    const u8* const at = g_gen_counters.load();
+    if (!at || at != d->framesBuf) return -1;                                         // no generate call since the buffer last moved
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(h, at, sizeof h, hipMemcpyDeviceToHost) != hipSuccess) return -(int)ZJNI_ERROR_no_device;
+    out4[0] = 0; out4[1] = g_gen_frames.load(); out4[2] = h[10]; out4[3] = 0;        // (no lane route yet: every frame takes the wave route)
+    return 0;
+}
+size_t zjni_mergeBlockDelimiters(zjni_sequence* seqs, size_t nSeqs) { return seqs ? zg_merge_block_delimiters((ZSSeq*)seqs, nSeqs) : 0; }
+size_t zjni_generate_sequences_batch_device(const void* d_src, const uint64_t* d_src_off, zjni_sequence* d_seqs, const uint64_t* d_seq_off,
+                                            uint64_t* d_result, size_t n, int level, int flags, void* stream) {
+    if (flags) return ZJNI_ERR(42);               // none is defined yet
+    if (level == 0) level = 3;                    // ZSTD_CLEVEL_DEFAULT
+    if (!zj_level_served(level)) return ZJNI_ERR(42);
+    if (n == 0) return 0;
+    if (n > 0xFFFFFFFFull) return ZJNI_ERR(72);
+    if (!d_src_off || !d_seq_off || !d_result) return ZJNI_ERR(42);
+    DevState* d = cur_state();
+    if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    BatchOrder order(d, stream);
+    hipStream_t st = (hipStream_t)stream;
+    u32 const lw = (u32)zj_level3_word((int)zs_level_word(level));
+    {   size_t const e = frames_room(d, 64, 0, st); if (e) return e; }
+    if (!ensure_multi_tables(d)) return ZJNI_ERR(64);
+    u32* const ctr = (u32*)d->framesBuf;
+    g_gen_counters.store(d->framesBuf); g_gen_frames.store((u32)n);
+    if (hipMemsetAsync(ctr, 0, 64, st) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    int const want = g_gen_grid.load();
+    size_t grid = (size_t)d->multiGrid; if (grid > n) grid = n; if (want > 0 && (size_t)want < grid) grid = (size_t)want;
+    hipLaunchKernelGGL(zj_generate_kernel, dim3((u32)grid), dim3(64), (u32)zj_up16(sizeof(ZXLds)), st, (const u8*)d_src, (const u64*)d_src_off, (ZSSeq*)d_seqs, (const u64*)d_seq_off,
+                       (u64*)d_result, lw, (u32)n, ctr + 4, d->encScratch, d->multiTables, ctr + 10);
+    return hipGetLastError() == hipSuccess ? 0 : ZJNI_ERR(ZJNI_ERROR_no_device);
+}
+// Host arrays: sources and slots go through one device buffer of the call's own (packed on the host, one copy each way).  Synchronous.
+size_t zjni_generate_sequences_batch(const void* const* src, const size_t* srcSize, zjni_sequence* const* seqs, const size_t* seqCapacity, size_t* result, size_t n, int level, int flags) {
+    if (flags) return ZJNI_ERR(42);
+    if (level == 0) level = 3;
+    if (!zj_level_served(level)) return ZJNI_ERR(42);
+    if (n == 0) return 0;
+    if (n > 0xFFFFFFFFull) return ZJNI_ERR(72);
+    if (!src || !srcSize || !seqs || !seqCapacity || !result) return ZJNI_ERR(42);
+    std::vector<u64> off(2 * (n + 1));
+    u64* const so = off.data(); u64* const qo = so + n + 1;
+    so[0] = qo[0] = 0;
+    for (size_t i = 0; i < n; i++) {
+        if ((srcSize[i] && !src[i]) || (seqCapacity[i] && !seqs[i])) return ZJNI_ERR(72);
+        if (srcSize[i] > ((size_t)1 << 40) || seqCapacity[i] > ((size_t)1 << 36)) return ZJNI_ERR(64);
+        so[i + 1] = so[i] + srcSize[i]; qo[i + 1] = qo[i] + seqCapacity[i];
+    }
+    if (!cur_state()) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    size_t const aOff = zj_up16(so[n]), inBytes = aOff + off.size() * 8;
+    size_t const aRes = zj_up16(inBytes), aSeq = aRes + zj_up16(n * 8), all = aSeq + qo[n] * 16;
+    std::vector<u8> image(inBytes);
+    for (size_t i = 0; i < n; i++) if (srcSize[i]) memcpy(image.data() + so[i], src[i], srcSize[i]);
+    memcpy(image.data() + aOff, off.data(), off.size() * 8);
+    u8* buf = nullptr;
+    if (hipMalloc(&buf, all ? all : 1) != hipSuccess) { (void)hipGetLastError(); return ZJNI_ERR(64); }
+    size_t r = 0;
+    if (hipMemcpy(buf, image.data(), inBytes, hipMemcpyHostToDevice) != hipSuccess) r = ZJNI_ERR(ZJNI_ERROR_no_device);
+    const u64* const dOff = (const u64*)(buf + aOff);
+    if (r == 0) r = zjni_generate_sequences_batch_device(buf, dOff, (zjni_sequence*)(buf + aSeq), dOff + n + 1, (uint64_t*)(buf + aRes), n, level, flags, nullptr);
+    std::vector<u8> back(all - aRes);
+    if (r == 0 && (hipStreamSynchronize(nullptr) != hipSuccess || hipMemcpy(back.data(), buf + aRes, all - aRes, hipMemcpyDeviceToHost) != hipSuccess)) r = ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (hipDeviceSynchronize() != hipSuccess && r == 0) r = ZJNI_ERR(ZJNI_ERROR_no_device);       // nothing may still use `buf`
+    (void)hipFree(buf);
+    if (r) return r;
+    const u64* const res = (const u64*)back.data();
+    for (size_t i = 0; i < n; i++) {
+        result[i] = (size_t)res[i];
+        if (!zjni_isError((size_t)res[i]) && res[i] <= seqCapacity[i] && res[i]) memcpy(seqs[i], back.data() + (aSeq - aRes) + qo[i] * 16, (size_t)res[i] * 16);
+    }
+    return 0;
+}
+size_t zjni_generate_sequences(zjni_sequence* seqs, size_t seqCapacity, const void* src, size_t srcSize, int level) {
+    size_t res = 0; const void* s = src; zjni_sequence* q = seqs;
+    size_t const r = zjni_generate_sequences_batch(&s, &srcSize, &q, &seqCapacity, &res, 1, level, 0);
+    return zjni_isError(r) ? r : res;
+}
 // ---- frame-parallel decompress ----
 // first walk, one lane per buffer as zj_inspect_kernel walks: cnt[i] = entries of buffer i
 __global__ __launch_bounds__(64) void zj_frames_count_kernel(const u8* __restrict__ src, const u64* __restrict__ off, u64* __restrict__ cnt, u32 n, u32* stat) {
