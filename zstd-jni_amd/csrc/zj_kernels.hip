@@ -17,6 +17,7 @@
 #include <system_error>
 #include <memory>
 #include <vector>
+#include <initializer_list>
 #include <string.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -1250,6 +1251,8 @@ struct DevState {
     std::atomic<unsigned>* slotTicket = nullptr;
     std::mutex* hostDecompMu = nullptr;
     u32* multiTables = nullptr; int multiGrid = 0;    // multi-block frames: frame-wide hash tables, one set per resident workgroup
+    int seqGrid = 0;                                  // resident workgroups of zj_encode_sequences_kernel (0: not asked yet)
+    const u8* genCounters = nullptr; u32 genFrames = 0;     // the last generate call: where its counters are (framesBuf as it was then) and its frames (zjni_last_generate)
     int contGrid = 0;                                 // resident workgroups of zj_encode_stream_continue_kernel (0: not asked yet)
     u32 lastPipeMax = 0;                              // what the last compress call passed to zj_pipe_route (diagnostics: zjni_last_lists)
     int pipeGrid = 0;                                 // ... and the resident workgroups of the pipelined kernel (two waves, two scratch slots each); 0: not available
@@ -1434,6 +1437,36 @@ struct SlotLock {
     }
     ~SlotLock() { if (s) s->mu.unlock(); }
     SlotLock(const SlotLock&) = delete; SlotLock& operator=(const SlotLock&) = delete;
+};
+// One host buffer through a staging slot, blocking: the slot (held until the guard goes), `total` bytes of its staging areas, and a drain of its kernel stream on
+// the way out — an error return leaves copies in flight on the staging area: none when the slot is given back.  A region has the same offset on both sides.
+struct StagedCall {
+    SlotLock lock;
+    bool const ready;                                 // false: no staging area (the caller answers ZJNI_ERROR_unsupported)
+    u8* const host; u8* const dev; hipStream_t const st;
+    StagedCall(DevState* d, size_t total) : lock(d), ready(ensure_staging(lock.s, total)), host(lock.s->hPinned), dev(lock.s->dStage), st(lock.s->hostK) {}
+    ~StagedCall() { if (ready) (void)hipStreamSynchronize(st); }
+    u64* words() const { return (u64*)host; }
+    // the first k bytes (header words, source) to the device; no wait
+    bool upload(size_t k) { return hipMemcpyAsync(dev, host, k, hipMemcpyHostToDevice, st) == hipSuccess; }
+    // header words [w0, w0 + k) back, and a wait
+    bool fetch(size_t w0, size_t k) {
+        return hipMemcpyAsync(host + w0 * 8, dev + w0 * 8, k * 8, hipMemcpyDeviceToHost, st) == hipSuccess && hipStreamSynchronize(st) == hipSuccess;
+    }
+    // regions back into the caller's buffers behind one wait
+    struct Span { void* to; size_t off, bytes; };
+    bool download(std::initializer_list<Span> spans) {
+        for (const Span& s : spans) if (s.bytes && hipMemcpyAsync(host + s.off, dev + s.off, s.bytes, hipMemcpyDeviceToHost, st) != hipSuccess) return false;
+        if (hipStreamSynchronize(st) != hipSuccess) return false;
+        for (const Span& s : spans) if (s.bytes) memcpy(s.to, host + s.off, s.bytes);
+        return true;
+    }
+    // what the entries with one result word and one payload end on: the word's checks, then its bytes out
+    size_t payload(size_t res, void* dst, size_t dstCap, size_t oDst) {
+        if (zjni_isError(res) || res == 0) return res;
+        if (res > dstCap) return ZJNI_ERR(ZJNI_ERROR_no_device);
+        return download({{dst, oDst, res}}) ? res : ZJNI_ERR(ZJNI_ERROR_no_device);
+    }
 };
 // Host-side copies of the host-pointer entries (caller's buffers <-> pinned staging) run on a few threads: one memcpy stream moves
 // ~10 GB/s, the PCIe link 57 each way — every byte of a batch is copied once by the host on each side, so these copies, not the link,
@@ -3680,12 +3713,20 @@ size_t zjni_pack_batch_device(const void* d_src, const uint64_t* d_src_off, cons
 
 // ============================================================================ large buffers as many frames (zj_frames.h) ============
 // zjni_decompress_frames_batch_device and zjni_compress_chunked_batch_device turn n large buffers into E small entries on the device, run the existing batch
-// pipelines on the entries and fold the entries' answers back into one per buffer.  No existing kernel changes: the pipelines take their batch size by value and size
-// their scratch on the host, so the one thing the host has to know is E — eight bytes read back through pinned memory behind the count and its scan, the only
-// host wait of either entry.  Everything else follows on `stream` in order.
+// pipelines on the entries and fold the entries' answers back into one per buffer.  The pipelines take their batch size by value and size their scratch on the
+// host, so the one thing the host has to know is E — eight bytes read back through pinned memory behind the count and its scan, the only host wait of either
+// entry.  Everything else follows on `stream` in order.
 //
 // framesBuf holds, per call: the per-buffer arrays (counts, their scans, carries), the per-entry arrays and, for the chunked compress, the entries' scratch
 // destinations of one slice.
+//
+// What every entry of this section shares is written once: frames_room and frames_read_total (framesBuf and a scan's totals, the one host wait), the range tail
+// of the two range entries (RangePlan: range_plan_read, range_plan_decode, range_plan_scatter) and their finish loop (zj_range_finish_body), StagedCall for the
+// blocking forms for one host buffer, packed_call for the host batch forms of the sequence entries, frames_stat_get behind the zjni_last_* getters, and the
+// argument rules zj_level_arg, dict_on_this_device and grid_cap.  A new entry brings its own arithmetic and calls these.
+static bool zj_level_arg(int& level) { if (level == 0) level = 3; return zj_level_served(level); }      // 0 = ZSTD_CLEVEL_DEFAULT, as ZSTD_c_compressionLevel = 0 means
+static bool dict_on_this_device(int ordinal) { return ordinal == t_dev || t_dev < 0; }                  // (else: digested on another device, 32)
+static u32 grid_cap(const DevState* d, size_t n) { return (u32)(n < (size_t)d->numCU * 8 ? n : (size_t)d->numCU * 8); }      // a wave or workgroup per item, eight per CU at most
 static bool frames_state(DevState* d) {
     if (!d->framesStat && hipMalloc(&d->framesStat, 64) != hipSuccess) { d->framesStat = nullptr; (void)hipGetLastError(); return false; }
     if (!d->framesE) {
@@ -3709,14 +3750,40 @@ static size_t frames_room(DevState* d, size_t need, size_t keep, hipStream_t st)
     d->framesBuf = fresh; d->framesBufCap = cap;
     return 0;
 }
-// first[n] (a scan's total = E) -> the host.  The wait is for the count kernel and its scan only (and for whatever the stream held before them).
-static size_t frames_read_total(DevState* d, const u64* d_total, hipStream_t st, u64* out) {
-    if (hipMemcpyAsync((void*)d->framesE, d_total, 8, hipMemcpyDeviceToHost, st) != hipSuccess || hipEventRecord(d->evFramesE, st) != hipSuccess
-        || hipEventSynchronize(d->evFramesE) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
-    *out = d->framesE[0];
+// k consecutive words (scan totals: first[n] = E) -> out[0 .. k) on the host, and one word more from d_also, when given, -> out[k]; 8 words at most.  The entry's one host
+// wait: for the count kernel and its scan only (and for whatever the stream held before them).
+static size_t frames_read_total(DevState* d, const u64* d_words, size_t k, hipStream_t st, u64* out, const u64* d_also = nullptr) {
+    if (hipMemcpyAsync((void*)d->framesE, d_words, k * 8, hipMemcpyDeviceToHost, st) != hipSuccess
+        || (d_also && hipMemcpyAsync((void*)(d->framesE + k), d_also, 8, hipMemcpyDeviceToHost, st) != hipSuccess)
+        || hipEventRecord(d->evFramesE, st) != hipSuccess || hipEventSynchronize(d->evFramesE) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    for (size_t i = 0; i < k + (d_also ? 1 : 0); i++) out[i] = d->framesE[i];
     return 0;
 }
 static inline size_t zj_up16(size_t v) { return (v + 15) & ~(size_t)15; }
+// the counters of one entry (four words of framesStat from `word`) behind everything the device holds; zeros while no call has made them
+static int frames_stat_get(u32 word, unsigned out4[4]) {
+    DevState* d = cur_state();
+    if (!d || !out4) return -(int)ZJNI_ERROR_no_device;
+    u32 h[4] = {0, 0, 0, 0};
+    if (hipDeviceSynchronize() != hipSuccess || (d->framesStat && hipMemcpy(h, d->framesStat + word, sizeof h, hipMemcpyDeviceToHost) != hipSuccess)) return -(int)ZJNI_ERROR_no_device;
+    for (int k = 0; k < 4; k++) out4[k] = h[k];
+    return 0;
+}
+// A host batch through one device buffer of the call's own, synchronous: `image` (packed on the host) goes to the buffer's front, run(buf) enqueues the device
+// entry on the null stream, [aRes, all) — results, then payload — comes back in `back`.  One copy each way.
+extern "C++" { template <class Run>      // (a template cannot have C linkage)
+static size_t packed_call(const std::vector<u8>& image, size_t aRes, size_t all, std::vector<u8>& back, Run run) {
+    u8* buf = nullptr;
+    if (hipMalloc(&buf, all ? all : 1) != hipSuccess) { (void)hipGetLastError(); return ZJNI_ERR(64); }
+    size_t r = 0;
+    if (hipMemcpy(buf, image.data(), image.size(), hipMemcpyHostToDevice) != hipSuccess) r = ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (r == 0) r = run(buf);
+    back.resize(all - aRes);
+    if (r == 0 && (hipStreamSynchronize(nullptr) != hipSuccess || hipMemcpy(back.data(), buf + aRes, all - aRes, hipMemcpyDeviceToHost) != hipSuccess)) r = ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (hipDeviceSynchronize() != hipSuccess && r == 0) r = ZJNI_ERR(ZJNI_ERROR_no_device);       // nothing may still use `buf`
+    (void)hipFree(buf);
+    return r;
+} }
 
 // ---- frames from the caller's sequences: ZSTD_compressSequences for batches (zj_sequences.h) ----
 // Two launches on `stream`, nothing else: the conversion (a wave per frame from a work counter) and the frame loop (a workgroup per frame from a second one).
@@ -3772,8 +3839,7 @@ size_t zjni_compress_sequences_batch_device(const void* d_src, const uint64_t* d
                                             void* d_dst, const uint64_t* d_dst_off, uint64_t* d_result, size_t n, int level, int flags, void* stream) {
     static_assert(sizeof(zjni_sequence) == 16 && sizeof(ZSSeq) == 16 && ZJNI_SEQ_REPCODES == ZS_FLAG_REPCODES && ZJNI_FRAME_CHECKSUM == ZE_FLAG_CHECKSUM, "zjni_sequence is ZSTD_Sequence");
     if (flags & ~(ZJNI_FRAME_CHECKSUM | ZJNI_SEQ_REPCODES)) return ZJNI_ERR(42);
-    if (level == 0) level = 3;                    // ZSTD_CLEVEL_DEFAULT
-    if (!zj_level_served(level)) return ZJNI_ERR(42);
+    if (!zj_level_arg(level)) return ZJNI_ERR(42);
     if (n == 0) return 0;
     if (n > 0x7FFFFFFFull) return ZJNI_ERR(72);
     if (!d_src_off || !d_seq_off || !d_dst_off || !d_result) return ZJNI_ERR(42);
@@ -3783,7 +3849,7 @@ size_t zjni_compress_sequences_batch_device(const void* d_src, const uint64_t* d
     hipStream_t st = (hipStream_t)stream;
     if (!frames_state(d)) return ZJNI_ERR(64);
     u64 total = 0;
-    {   size_t const e = frames_read_total(d, d_seq_off + n, st, &total); if (e) return e; }
+    {   size_t const e = frames_read_total(d, (const u64*)d_seq_off + n, 1, st, &total); if (e) return e; }
     if (total > ((u64)1 << 40)) return ZJNI_ERR(64);
     if (total && !d_seqs) return ZJNI_ERR(42);
     size_t const slots = (size_t)total + n;
@@ -3791,24 +3857,19 @@ size_t zjni_compress_sequences_batch_device(const void* d_src, const uint64_t* d
     {   size_t const e = frames_room(d, need, 0, st); if (e) return e; }
     u32* const ctr = (u32*)d->framesBuf;
     if (hipMemsetAsync(ctr, 0, 64, st) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
-    static std::mutex gridMu; static std::map<int, int> gridOf;                      // resident workgroups of the frame loop per device, asked for once
-    int grid;
-    {   std::lock_guard<std::mutex> lk(gridMu);
-        auto it = gridOf.find(d->ordinal);
-        if (it == gridOf.end()) {
-            int perCU = 0;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, zj_encode_sequences_kernel, 64, sizeof(ZEEntropy)) != hipSuccess || perCU < 1) { (void)hipGetLastError(); perCU = 1; }
-            int gmax = d->numCU * perCU;
-            if (gmax > d->encGrid) gmax = d->encGrid;                                // a scratch slot per workgroup
-            it = gridOf.emplace(d->ordinal, gmax).first;
-        }
-        grid = it->second; }
+    if (!d->seqGrid) {                                                               // resident workgroups of the frame loop, asked for once (under BatchOrder)
+        int perCU = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCU, zj_encode_sequences_kernel, 64, sizeof(ZEEntropy)) != hipSuccess || perCU < 1) { (void)hipGetLastError(); perCU = 1; }
+        d->seqGrid = d->numCU * perCU;
+        if (d->seqGrid > d->encGrid) d->seqGrid = d->encGrid;                        // a scratch slot per workgroup
+    }
+    int grid = d->seqGrid;
     int const want = g_seq_grid.load();
     if (want > 0 && want < grid) grid = want;
     if ((size_t)grid > n) grid = (int)n;
     u32 const lw = zs_level_word(level);
     ZESeq* const rec = (ZESeq*)(d->framesBuf + offRec); u32* const lit = (u32*)(d->framesBuf + offLit); u32* const nBlk = (u32*)(d->framesBuf + offNblk);
-    size_t convGrid = (size_t)d->numCU * 8; if (convGrid > n) convGrid = n; if (want > 0 && (size_t)want < convGrid) convGrid = (size_t)want;
+    size_t convGrid = grid_cap(d, n); if (want > 0 && (size_t)want < convGrid) convGrid = (size_t)want;
     hipLaunchKernelGGL(zj_seq_convert_kernel, dim3((u32)convGrid), dim3(64), 0, st, (const u64*)d_src_off, (const ZSSeq*)d_seqs, (const u64*)d_seq_off, total, rec, lit, nBlk, (u32)n, lw, (u32)flags, ctr);
     if (hipGetLastError() != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
     hipLaunchKernelGGL(zj_encode_sequences_kernel, dim3((u32)grid), dim3(64), sizeof(ZEEntropy), st, (const u8*)d_src, (const u64*)d_src_off, (const u64*)d_seq_off, (u8*)d_dst,
@@ -3819,8 +3880,7 @@ size_t zjni_compress_sequences_batch_device(const void* d_src, const uint64_t* d
 size_t zjni_compress_sequences_batch(const void* const* src, const size_t* srcSize, const zjni_sequence* const* seqs, const size_t* nSeqs,
                                      void* const* dst, const size_t* dstCap, size_t* result, size_t n, int level, int flags) {
     if (flags & ~(ZJNI_FRAME_CHECKSUM | ZJNI_SEQ_REPCODES)) return ZJNI_ERR(42);
-    if (level == 0) level = 3;
-    if (!zj_level_served(level)) return ZJNI_ERR(42);
+    if (!zj_level_arg(level)) return ZJNI_ERR(42);
     if (n == 0) return 0;
     if (n > 0x7FFFFFFFull) return ZJNI_ERR(72);
     if (!src || !srcSize || !seqs || !nSeqs || !dst || !dstCap || !result) return ZJNI_ERR(42);
@@ -3841,16 +3901,11 @@ size_t zjni_compress_sequences_batch(const void* const* src, const size_t* srcSi
         if (nSeqs[i]) memcpy(image.data() + aSeq + qo[i] * 16, seqs[i], nSeqs[i] * 16);
     }
     memcpy(image.data() + aOff, off.data(), off.size() * 8);
-    u8* buf = nullptr;
-    if (hipMalloc(&buf, all ? all : 1) != hipSuccess) { (void)hipGetLastError(); return ZJNI_ERR(64); }
-    size_t r = 0;
-    if (hipMemcpy(buf, image.data(), inBytes, hipMemcpyHostToDevice) != hipSuccess) r = ZJNI_ERR(ZJNI_ERROR_no_device);
-    const u64* const dOff = (const u64*)(buf + aOff);
-    if (r == 0) r = zjni_compress_sequences_batch_device(buf + aSrc, dOff, (const zjni_sequence*)(buf + aSeq), dOff + n + 1, buf + aDst, dOff + 2 * (n + 1), (uint64_t*)(buf + aRes), n, level, flags, nullptr);
-    std::vector<u8> back(all - aRes);
-    if (r == 0 && (hipStreamSynchronize(nullptr) != hipSuccess || hipMemcpy(back.data(), buf + aRes, all - aRes, hipMemcpyDeviceToHost) != hipSuccess)) r = ZJNI_ERR(ZJNI_ERROR_no_device);
-    if (hipDeviceSynchronize() != hipSuccess && r == 0) r = ZJNI_ERR(ZJNI_ERROR_no_device);       // nothing may still use `buf`
-    (void)hipFree(buf);
+    std::vector<u8> back;
+    size_t const r = packed_call(image, aRes, all, back, [&](u8* buf) {
+        const u64* const dOff = (const u64*)(buf + aOff);
+        return zjni_compress_sequences_batch_device(buf + aSrc, dOff, (const zjni_sequence*)(buf + aSeq), dOff + n + 1, buf + aDst, dOff + 2 * (n + 1), (uint64_t*)(buf + aRes), n, level, flags, nullptr);
+    });
     if (r) return r;
     const u64* const res = (const u64*)back.data();
     for (size_t i = 0; i < n; i++) {
@@ -3891,25 +3946,22 @@ __global__ __launch_bounds__(64, ZJ_MULTI_WAVES) void zj_generate_kernel(const u
     }
 }
 static std::atomic<int> g_gen_grid(0);           // zjni_debug_generate_grid
-static std::atomic<const u8*> g_gen_counters(nullptr);      // where the last generate call's counters are (zjni_last_generate)
-static std::atomic<u32> g_gen_frames(0);                    // ... and how many frames it had
 int zjni_debug_generate_grid(int grid) { return g_gen_grid.exchange(grid < 0 ? 0 : grid); }
 int zjni_last_generate(unsigned out4[4]) {
     DevState* d = cur_state();
     if (!d || !out4) return -(int)ZJNI_ERROR_no_device;
     u32 h[16];
-    const u8* const at = g_gen_counters.load();
+    const u8* const at = d->genCounters;
     if (!at || at != d->framesBuf) return -1;                                         // no generate call since the buffer last moved
     if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(h, at, sizeof h, hipMemcpyDeviceToHost) != hipSuccess) return -(int)ZJNI_ERROR_no_device;
-    out4[0] = 0; out4[1] = g_gen_frames.load(); out4[2] = h[10]; out4[3] = 0;        // (no lane route yet: every frame takes the wave route)
+    out4[0] = 0; out4[1] = d->genFrames; out4[2] = h[10]; out4[3] = 0;               // (no lane route yet: every frame takes the wave route)
     return 0;
 }
 size_t zjni_mergeBlockDelimiters(zjni_sequence* seqs, size_t nSeqs) { return seqs ? zg_merge_block_delimiters((ZSSeq*)seqs, nSeqs) : 0; }
 size_t zjni_generate_sequences_batch_device(const void* d_src, const uint64_t* d_src_off, zjni_sequence* d_seqs, const uint64_t* d_seq_off,
                                             uint64_t* d_result, size_t n, int level, int flags, void* stream) {
     if (flags) return ZJNI_ERR(42);               // none is defined yet
-    if (level == 0) level = 3;                    // ZSTD_CLEVEL_DEFAULT
-    if (!zj_level_served(level)) return ZJNI_ERR(42);
+    if (!zj_level_arg(level)) return ZJNI_ERR(42);
     if (n == 0) return 0;
     if (n > 0xFFFFFFFFull) return ZJNI_ERR(72);
     if (!d_src_off || !d_seq_off || !d_result) return ZJNI_ERR(42);
@@ -3921,7 +3973,7 @@ size_t zjni_generate_sequences_batch_device(const void* d_src, const uint64_t* d
     {   size_t const e = frames_room(d, 64, 0, st); if (e) return e; }
     if (!ensure_multi_tables(d)) return ZJNI_ERR(64);
     u32* const ctr = (u32*)d->framesBuf;
-    g_gen_counters.store(d->framesBuf); g_gen_frames.store((u32)n);
+    d->genCounters = d->framesBuf; d->genFrames = (u32)n;
     if (hipMemsetAsync(ctr, 0, 64, st) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
     int const want = g_gen_grid.load();
     size_t grid = (size_t)d->multiGrid; if (grid > n) grid = n; if (want > 0 && (size_t)want < grid) grid = (size_t)want;
@@ -3932,8 +3984,7 @@ size_t zjni_generate_sequences_batch_device(const void* d_src, const uint64_t* d
 // Host arrays: sources and slots go through one device buffer of the call's own (packed on the host, one copy each way).  Synchronous.
 size_t zjni_generate_sequences_batch(const void* const* src, const size_t* srcSize, zjni_sequence* const* seqs, const size_t* seqCapacity, size_t* result, size_t n, int level, int flags) {
     if (flags) return ZJNI_ERR(42);
-    if (level == 0) level = 3;
-    if (!zj_level_served(level)) return ZJNI_ERR(42);
+    if (!zj_level_arg(level)) return ZJNI_ERR(42);
     if (n == 0) return 0;
     if (n > 0xFFFFFFFFull) return ZJNI_ERR(72);
     if (!src || !srcSize || !seqs || !seqCapacity || !result) return ZJNI_ERR(42);
@@ -3951,16 +4002,11 @@ size_t zjni_generate_sequences_batch(const void* const* src, const size_t* srcSi
     std::vector<u8> image(inBytes);
     for (size_t i = 0; i < n; i++) if (srcSize[i]) memcpy(image.data() + so[i], src[i], srcSize[i]);
     memcpy(image.data() + aOff, off.data(), off.size() * 8);
-    u8* buf = nullptr;
-    if (hipMalloc(&buf, all ? all : 1) != hipSuccess) { (void)hipGetLastError(); return ZJNI_ERR(64); }
-    size_t r = 0;
-    if (hipMemcpy(buf, image.data(), inBytes, hipMemcpyHostToDevice) != hipSuccess) r = ZJNI_ERR(ZJNI_ERROR_no_device);
-    const u64* const dOff = (const u64*)(buf + aOff);
-    if (r == 0) r = zjni_generate_sequences_batch_device(buf, dOff, (zjni_sequence*)(buf + aSeq), dOff + n + 1, (uint64_t*)(buf + aRes), n, level, flags, nullptr);
-    std::vector<u8> back(all - aRes);
-    if (r == 0 && (hipStreamSynchronize(nullptr) != hipSuccess || hipMemcpy(back.data(), buf + aRes, all - aRes, hipMemcpyDeviceToHost) != hipSuccess)) r = ZJNI_ERR(ZJNI_ERROR_no_device);
-    if (hipDeviceSynchronize() != hipSuccess && r == 0) r = ZJNI_ERR(ZJNI_ERROR_no_device);       // nothing may still use `buf`
-    (void)hipFree(buf);
+    std::vector<u8> back;
+    size_t const r = packed_call(image, aRes, all, back, [&](u8* buf) {
+        const u64* const dOff = (const u64*)(buf + aOff);
+        return zjni_generate_sequences_batch_device(buf, dOff, (zjni_sequence*)(buf + aSeq), dOff + n + 1, (uint64_t*)(buf + aRes), n, level, flags, nullptr);
+    });
     if (r) return r;
     const u64* const res = (const u64*)back.data();
     for (size_t i = 0; i < n; i++) {
@@ -4012,7 +4058,7 @@ __global__ __launch_bounds__(64) void zj_frames_reduce_kernel(const u64* __restr
 }
 size_t zjni_decompress_frames_batch_device(const void* d_src, const uint64_t* d_src_off, void* d_dst, const uint64_t* d_dst_off,
                                            uint64_t* d_result, size_t n, const zjni_ddict* ddict, void* stream) {
-    if (ddict && ddict->ordinal != t_dev && t_dev >= 0) return ZJNI_ERR(32);      // digested on another device
+    if (ddict && !dict_on_this_device(ddict->ordinal)) return ZJNI_ERR(32);
     DevState* d = cur_state();
     if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
     if (n > 0xFFFFFFFFull) return ZJNI_ERR(72);
@@ -4029,7 +4075,7 @@ size_t zjni_decompress_frames_batch_device(const void* d_src, const uint64_t* d_
     hipLaunchKernelGGL(zj_frames_count_kernel, dim3((u32)((n + 63) / 64)), dim3(64), 0, st, (const u8*)d_src, (const u64*)d_src_off, (u64*)(d->framesBuf + oCnt), (u32)n, d->framesStat);
     hipLaunchKernelGGL(zj_pack_offsets_kernel, dim3(1), dim3(1024), 0, st, (const u64*)(d->framesBuf + oCnt), (u64*)(d->framesBuf + oFirst), (u32)n);
     u64 E = 0;
-    if ((r = frames_read_total(d, (const u64*)(d->framesBuf + oFirst) + n, st, &E)) != 0) return r;
+    if ((r = frames_read_total(d, (const u64*)(d->framesBuf + oFirst) + n, 1, st, &E)) != 0) return r;
     if (E > 0xFFFFFFFFull) return ZJNI_ERR(72);
     if (E < n) return ZJNI_ERR(ZJNI_ERROR_no_device);                           // (every buffer is at least one entry)
     // per entry: [srcOffE E + 1][dstOffE E + 1][resE E]
@@ -4040,8 +4086,7 @@ size_t zjni_decompress_frames_batch_device(const void* d_src, const uint64_t* d_
                        (u64*)(fb + oSrcE), (u64*)(fb + oDstE), (u32)n);
     if (hipGetLastError() != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
     if ((r = decompress_chunked_ordered(d_src, (const u64*)(fb + oSrcE), d_dst, (const u64*)(fb + oDstE), (u64*)(fb + oResE), (size_t)E, ddict, stream)) != 0) return r;
-    u32 const gridR = (u32)(n < (size_t)d->numCU * 8 ? n : (size_t)d->numCU * 8);
-    hipLaunchKernelGGL(zj_frames_reduce_kernel, dim3(gridR), dim3(64), 0, st, (const u64*)(fb + oFirst), (const u64*)(fb + oResE), (u64*)d_result, (u32)n, (u32*)(fb + oRedo), d->framesStat);
+    hipLaunchKernelGGL(zj_frames_reduce_kernel, dim3(grid_cap(d, n)), dim3(64), 0, st, (const u64*)(fb + oFirst), (const u64*)(fb + oResE), (u64*)d_result, (u32)n, (u32*)(fb + oRedo), d->framesStat);
     // the redo list: the fused kernel over the caller's own offsets, one wave per buffer; whatever it answers stands (an empty list is a launch that finds no work)
     if (ddict) {
         u32 const gridD = (u32)(n < (size_t)d->decDictGrid ? n : (size_t)d->decDictGrid);
@@ -4056,12 +4101,9 @@ size_t zjni_decompress_frames_batch_device(const void* d_src, const uint64_t* d_
     return hipGetLastError() == hipSuccess ? 0 : ZJNI_ERR(ZJNI_ERROR_no_device);
 }
 int zjni_last_frames(unsigned* out4) {
-    DevState* d = cur_state();
-    if (!d || !out4) return -(int)ZJNI_ERROR_no_device;
-    u32 h[4] = {0, 0, 0, 0};
-    if (hipDeviceSynchronize() != hipSuccess || (d->framesStat && hipMemcpy(h, d->framesStat, sizeof h, hipMemcpyDeviceToHost) != hipSuccess)) return -(int)ZJNI_ERROR_no_device;
-    out4[0] = h[0]; out4[1] = (unsigned)d->lastFramesE; out4[2] = h[1]; out4[3] = h[2];
-    return 0;
+    int const r = frames_stat_get(0, out4);
+    if (r == 0) { out4[3] = out4[2]; out4[2] = out4[1]; out4[1] = (unsigned)cur_state()->lastFramesE; }      // the entries decoded are the host's count
+    return r;
 }
 
 // ---- ranged decompress (zj_frames_range.h) ----
@@ -4138,37 +4180,93 @@ __global__ __launch_bounds__(256) void zj_range_gather_kernel(const ZRCopy* __re
         if (t < pl.tail) db[(pl.body << 4) + t] = sb[(pl.body << 4) + t];
     }
 }
-// One wave per buffer: the first error over its entries in frame order (edge first, interiors, edge last), the result, the stats (stat[4 .. 8)); a buffer with an
-// error gets its edge runs emptied, so the gather behind this kernel copies nothing for it.
-__global__ __launch_bounds__(64) void zj_range_finish_kernel(const ZRRec* __restrict__ rec, const u64* __restrict__ scan, const u64* __restrict__ resA, const u64* __restrict__ resB,
-                                                             u64* __restrict__ result, u32 n, ZRCopy* __restrict__ out, u32* stat) {
+// The finish loop of both range entries.  One wave per buffer (or request): the first error over its entries in frame order (edge first, interiors, edge last),
+// the result, the stats (stat[P::kStat .. + 4)); a buffer with an error gets its edge runs emptied, so the gather behind the kernel copies nothing for it.
+// The policy P says what a buffer starts with (initial), and what an entry's answer counts as, 0 or an error (edge: first or last; interior: the k-th).
+extern "C++" { template <class P>      // (a template cannot have C linkage)
+__device__ __forceinline__ void zj_range_finish_body(const P& p, const ZRRec* __restrict__ rec, const u64* __restrict__ scan, const u64* __restrict__ resA, const u64* __restrict__ resB,
+                                                     u64* __restrict__ result, u32 n, ZRCopy* __restrict__ out, u32* stat) {
     u32 const lane = threadIdx.x;
     for (u32 i = blockIdx.x; i < n; i += gridDim.x) {
         u32 const status = rec[i].status, e = rec[i].edges, frames = rec[i].frames;
         if (status != ZJ_RANGE_SELECTED) {
-            if (lane == 0) { result[i] = status == ZJ_RANGE_NOTHING ? 0 : ZJ_ERR64(status); atomicAdd(&stat[status == ZJ_RANGE_NOTHING ? 4 : 7], 1u); }
+            if (lane == 0) { result[i] = status == ZJ_RANGE_NOTHING ? 0 : ZJ_ERR64(status); atomicAdd(&stat[P::kStat + (status == ZJ_RANGE_NOTHING ? 0 : 3)], 1u); }
             continue;
         }
         u64 const a0 = scan[i], m = scan[i + 1] - a0 - 1u, b0 = scan[(u64)n + 1u + i];
-        u64 err = 0;
-        if (e & 1u) { u64 const v = resB[b0]; if (v > ((u64)1 << 40)) err = v; }
+        u64 err = p.initial(i);
+        if (!err && (e & 1u)) err = p.edge(i, resB[b0], false);
         for (u64 base = 0; base < m && !err; base += 64) {
             u64 const k = base + lane;
-            u64 const v = k < m ? resA[a0 + k] : 0;
-            unsigned long long const mask = __ballot(v > ((u64)1 << 40));
+            u64 const v = k < m ? p.interior(i, k, resA[a0 + k]) : 0;
+            unsigned long long const mask = __ballot(v != 0);
             if (mask) err = __shfl(v, (int)(__ffsll((long long)mask) - 1), 64);
         }
-        if (!err && (e & 2u)) { u64 const v = resB[b0 + (e & 1u)]; if (v > ((u64)1 << 40)) err = v; }
+        if (!err && (e & 2u)) err = p.edge(i, resB[b0 + (e & 1u)], true);
         if (lane == 0) {
             result[i] = err ? err : rec[i].hi - rec[i].lo;
             if (err) { out[2 * (u64)i].len = 0; out[2 * (u64)i + 1].len = 0; }
-            atomicAdd(&stat[err ? 7 : 4], 1u); atomicAdd(&stat[5], frames); atomicAdd(&stat[6], zj_range_edge_count(e));
+            atomicAdd(&stat[P::kStat + (err ? 3 : 0)], 1u); atomicAdd(&stat[P::kStat + 1], frames); atomicAdd(&stat[P::kStat + 2], zj_range_edge_count(e));
         }
     }
+} }
+// the walked entry: an entry counts as the pipeline answered it
+struct ZRFinishWalked {
+    static constexpr u32 kStat = 4;
+    __device__ u64 initial(u32) const { return 0; }
+    __device__ u64 edge(u32, u64 v, bool) const { return v > ((u64)1 << 40) ? v : 0; }
+    __device__ u64 interior(u32, u64, u64 v) const { return v > ((u64)1 << 40) ? v : 0; }
+};
+__global__ __launch_bounds__(64) void zj_range_finish_kernel(const ZRRec* __restrict__ rec, const u64* __restrict__ scan, const u64* __restrict__ resA, const u64* __restrict__ resB,
+                                                             u64* __restrict__ result, u32 n, ZRCopy* __restrict__ out, u32* stat) {
+    zj_range_finish_body(ZRFinishWalked{}, rec, scan, resA, resB, result, n, out, stat);
+}
+// The tail of both range entries.  In front of it the entry has laid out framesBuf's first `head` bytes (its per-buffer or per-request arrays, the five totals at
+// oTot) and launched its count (or request) kernel and zj_range_scan_kernel over `count` buffers (or requests).
+struct RangePlan {
+    u64 EA, EB, CA, CB, SB;          // entries of set A, of set B, compact source bytes of A, of B, scratch bytes of the edge frames
+    // per entry and per run: [srcA EA + 1][dstA EA + 1][resA EA][srcB EB + 1][dstB EB + 1][resB EB][in 3 x count][out 2 x count][compact bytes CA + CB][edge scratch SB]
+    size_t oSrcA, oDstA, oResA, oSrcB, oDstB, oResB, oIn, oOut, oComp, oEdge, total;
+};
+static u64 range_tiles(u64 bytes) { return (bytes + ZJ_RANGE_TILE - 1) / ZJ_RANGE_TILE; }
+// the entry's only host wait (the five totals in one copy of 40 bytes: the pipelines size their launches on the host), their checks, the layout, and room for it
+static size_t range_plan_read(DevState* d, size_t oTot, size_t count, size_t head, hipStream_t st, RangePlan& p) {
+    u64 t[5];
+    size_t const r = frames_read_total(d, (const u64*)(d->framesBuf + oTot), 5, st, t);
+    if (r != 0) return r;
+    p.EA = t[0]; p.EB = t[1]; p.CA = t[2]; p.CB = t[3]; p.SB = t[4];
+    if (p.EA > 0xFFFFFFFFull) return ZJNI_ERR(72);
+    if (p.EA < count || p.EB > 2 * (u64)count) return ZJNI_ERR(ZJNI_ERROR_no_device);          // (every buffer has its closing entry and at most two edges)
+    p.oSrcA = head; p.oDstA = p.oSrcA + zj_up16((p.EA + 1) * 8); p.oResA = p.oDstA + zj_up16((p.EA + 1) * 8); p.oSrcB = p.oResA + zj_up16(p.EA * 8 + 8);
+    p.oDstB = p.oSrcB + zj_up16((p.EB + 1) * 8); p.oResB = p.oDstB + zj_up16((p.EB + 1) * 8); p.oIn = p.oResB + zj_up16(p.EB * 8 + 8);
+    p.oOut = p.oIn + zj_up16(3 * count * sizeof(ZRCopy)); p.oComp = p.oOut + zj_up16(2 * count * sizeof(ZRCopy));
+    p.oEdge = p.oComp + zj_up16(p.CA + p.CB) + 16; p.total = p.oEdge + zj_up16(p.SB) + 16;
+    if (p.CA + p.CB < p.CA || p.total < p.oComp || p.total < p.SB) return ZJNI_ERR(64);
+    return frames_room(d, p.total, head, st);
+}
+// behind the entry's emit launches: the selected source bytes into the compact area (3 x count runs), then the pipelines over set A (into the caller's slots) and
+// set B (into the edge scratch)
+static size_t range_plan_decode(DevState* d, const RangePlan& p, size_t count, const void* d_src, void* d_dst, const zjni_ddict* ddict, void* stream) {
+    u8* const fb = d->framesBuf;
+    u64 const tilesIn = range_tiles(p.CA + p.CB);
+    if (tilesIn > 0x7FFFFFFFull || range_tiles(p.SB) > 0x7FFFFFFFull) return ZJNI_ERR(64);
+    if (tilesIn) hipLaunchKernelGGL(zj_range_gather_kernel, dim3((u32)tilesIn), dim3(256), 0, (hipStream_t)stream, (const ZRCopy*)(fb + p.oIn), (u64)(3 * count), (const u8*)d_src, fb + p.oComp, 1u, p.CA + p.CB);
+    if (hipGetLastError() != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    size_t r = 0;
+    // (a call with no interior frame has nothing but closing entries in set A: no launch)
+    if (p.EA > count && (r = decompress_chunked_ordered(fb + p.oComp, (const u64*)(fb + p.oSrcA), d_dst, (const u64*)(fb + p.oDstA), (u64*)(fb + p.oResA), (size_t)p.EA, ddict, stream)) != 0) return r;
+    if (p.EB && (r = decompress_chunked_ordered(fb + p.oComp, (const u64*)(fb + p.oSrcB), fb + p.oEdge, (const u64*)(fb + p.oDstB), (u64*)(fb + p.oResB), (size_t)p.EB, ddict, stream)) != 0) return r;
+    return 0;
+}
+// behind the entry's finish launch: the edge frames' bytes from the scratch into the caller's slots (2 x count runs)
+static size_t range_plan_scatter(DevState* d, const RangePlan& p, size_t count, void* d_dst, hipStream_t st) {
+    u64 const tilesOut = range_tiles(p.SB);
+    if (tilesOut) hipLaunchKernelGGL(zj_range_gather_kernel, dim3((u32)tilesOut), dim3(256), 0, st, (const ZRCopy*)(d->framesBuf + p.oOut), (u64)(2 * count), (const u8*)(d->framesBuf + p.oEdge), (u8*)d_dst, 0u, p.SB);
+    return hipGetLastError() == hipSuccess ? 0 : ZJNI_ERR(ZJNI_ERROR_no_device);
 }
 size_t zjni_decompress_frames_range_batch_device(const void* d_src, const uint64_t* d_src_off, void* d_dst, const uint64_t* d_dst_off, const uint64_t* d_range,
                                                  uint64_t* d_result, uint64_t* d_total, size_t n, const zjni_ddict* ddict, void* stream) {
-    if (ddict && ddict->ordinal != t_dev && t_dev >= 0) return ZJNI_ERR(32);      // digested on another device
+    if (ddict && !dict_on_this_device(ddict->ordinal)) return ZJNI_ERR(32);
     DevState* d = cur_state();
     if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
     if (n > 0xFFFFFFFFull) return ZJNI_ERR(72);
@@ -4184,47 +4282,21 @@ size_t zjni_decompress_frames_range_batch_device(const void* d_src, const uint64
     hipLaunchKernelGGL(zj_range_count_kernel, dim3(gridN), dim3(64), 0, st, (const u8*)d_src, (const u64*)d_src_off, (const u64*)d_dst_off, (const u64*)d_range,
                        (ZRRec*)(d->framesBuf + oRec), (u64*)(d->framesBuf + oQ), (u64*)d_total, (u32)n);
     hipLaunchKernelGGL(zj_range_scan_kernel, dim3(5), dim3(1024), 0, st, (const u64*)(d->framesBuf + oQ), (u64*)(d->framesBuf + oScan), (u64*)(d->framesBuf + oTot), (u32)n);
-    // the entry's only host wait: the five totals in one copy
-    if (hipMemcpyAsync((void*)d->framesE, d->framesBuf + oTot, 40, hipMemcpyDeviceToHost, st) != hipSuccess || hipEventRecord(d->evFramesE, st) != hipSuccess
-        || hipEventSynchronize(d->evFramesE) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
-    u64 const EA = d->framesE[0], EB = d->framesE[1], CA = d->framesE[2], CB = d->framesE[3], SB = d->framesE[4];
-    if (EA > 0xFFFFFFFFull) return ZJNI_ERR(72);
-    if (EA < n || EB > 2 * (u64)n) return ZJNI_ERR(ZJNI_ERROR_no_device);          // (every buffer has its closing entry and at most two edges)
-    // per entry and per run: [srcA EA + 1][dstA EA + 1][resA EA][srcB EB + 1][dstB EB + 1][resB EB][in 3n][out 2n][compact bytes CA + CB][edge scratch SB]
-    size_t const oSrcA = perBuf, oDstA = oSrcA + zj_up16((EA + 1) * 8), oResA = oDstA + zj_up16((EA + 1) * 8), oSrcB = oResA + zj_up16(EA * 8 + 8),
-                 oDstB = oSrcB + zj_up16((EB + 1) * 8), oResB = oDstB + zj_up16((EB + 1) * 8), oIn = oResB + zj_up16(EB * 8 + 8), oOut = oIn + zj_up16(3 * n * sizeof(ZRCopy)),
-                 oComp = oOut + zj_up16(2 * n * sizeof(ZRCopy)), oEdge = oComp + zj_up16(CA + CB) + 16, total = oEdge + zj_up16(SB) + 16;
-    if (CA + CB < CA || total < oComp || total < SB) return ZJNI_ERR(64);
-    if ((r = frames_room(d, total, perBuf, st)) != 0) return r;
+    RangePlan p;
+    if ((r = range_plan_read(d, oTot, n, perBuf, st, p)) != 0) return r;
     u8* const fb = d->framesBuf;
-    ZRCopy* const in = (ZRCopy*)(fb + oIn); ZRCopy* const out = (ZRCopy*)(fb + oOut);
     hipLaunchKernelGGL(zj_range_emit_kernel, dim3(gridN), dim3(64), 0, st, (const u8*)d_src, (const u64*)d_src_off, (const u64*)d_dst_off, (const ZRRec*)(fb + oRec),
-                       (const u64*)(fb + oScan), (u32)n, (u64*)(fb + oSrcA), (u64*)(fb + oDstA), (u64*)(fb + oSrcB), (u64*)(fb + oDstB), in, out);
-    u64 const tilesIn = (CA + CB + ZJ_RANGE_TILE - 1) / ZJ_RANGE_TILE, tilesOut = (SB + ZJ_RANGE_TILE - 1) / ZJ_RANGE_TILE;
-    if (tilesIn > 0x7FFFFFFFull || tilesOut > 0x7FFFFFFFull) return ZJNI_ERR(64);
-    if (tilesIn) hipLaunchKernelGGL(zj_range_gather_kernel, dim3((u32)tilesIn), dim3(256), 0, st, (const ZRCopy*)in, (u64)(3 * n), (const u8*)d_src, fb + oComp, 1u, CA + CB);
-    if (hipGetLastError() != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
-    // (a call with no interior frame has nothing but closing entries in set A: no launch)
-    if (EA > n && (r = decompress_chunked_ordered(fb + oComp, (const u64*)(fb + oSrcA), d_dst, (const u64*)(fb + oDstA), (u64*)(fb + oResA), (size_t)EA, ddict, stream)) != 0) return r;
-    if (EB && (r = decompress_chunked_ordered(fb + oComp, (const u64*)(fb + oSrcB), fb + oEdge, (const u64*)(fb + oDstB), (u64*)(fb + oResB), (size_t)EB, ddict, stream)) != 0) return r;
-    u32 const gridF = (u32)(n < (size_t)d->numCU * 8 ? n : (size_t)d->numCU * 8);
-    hipLaunchKernelGGL(zj_range_finish_kernel, dim3(gridF), dim3(64), 0, st, (const ZRRec*)(fb + oRec), (const u64*)(fb + oScan), (const u64*)(fb + oResA), (const u64*)(fb + oResB),
-                       (u64*)d_result, (u32)n, out, d->framesStat);
-    if (tilesOut) hipLaunchKernelGGL(zj_range_gather_kernel, dim3((u32)tilesOut), dim3(256), 0, st, (const ZRCopy*)out, (u64)(2 * n), (const u8*)(fb + oEdge), (u8*)d_dst, 0u, SB);
-    return hipGetLastError() == hipSuccess ? 0 : ZJNI_ERR(ZJNI_ERROR_no_device);
+                       (const u64*)(fb + oScan), (u32)n, (u64*)(fb + p.oSrcA), (u64*)(fb + p.oDstA), (u64*)(fb + p.oSrcB), (u64*)(fb + p.oDstB), (ZRCopy*)(fb + p.oIn), (ZRCopy*)(fb + p.oOut));
+    if ((r = range_plan_decode(d, p, n, d_src, d_dst, ddict, stream)) != 0) return r;
+    hipLaunchKernelGGL(zj_range_finish_kernel, dim3(grid_cap(d, n)), dim3(64), 0, st, (const ZRRec*)(fb + oRec), (const u64*)(fb + oScan), (const u64*)(fb + p.oResA), (const u64*)(fb + p.oResB),
+                       (u64*)d_result, (u32)n, (ZRCopy*)(fb + p.oOut), d->framesStat);
+    return range_plan_scatter(d, p, n, d_dst, st);
 }
-int zjni_last_frames_range(unsigned* out4) {
-    DevState* d = cur_state();
-    if (!d || !out4) return -(int)ZJNI_ERROR_no_device;
-    u32 h[4] = {0, 0, 0, 0};
-    if (hipDeviceSynchronize() != hipSuccess || (d->framesStat && hipMemcpy(h, d->framesStat + 4, sizeof h, hipMemcpyDeviceToHost) != hipSuccess)) return -(int)ZJNI_ERROR_no_device;
-    for (int k = 0; k < 4; k++) out4[k] = h[k];
-    return 0;
-}
+int zjni_last_frames_range(unsigned* out4) { return frames_stat_get(4, out4); }
 
 // ---- range reads by a caller-held index (zj_index.h) ----
-// No kernel above is edited: the request kernel stands where zj_range_count_kernel stands, zj_range_scan_kernel runs with n := R, the entries of set A are written
-// one lane each, and zj_range_emit itself (with no interior entry to walk) writes set B and the copy runs of a request.
+// The request kernel stands where zj_range_count_kernel stands, zj_range_scan_kernel runs with n := R, the entries of set A are written one lane each, and
+// zj_range_emit itself (with no interior entry to walk) writes set B and the copy runs of a request.
 size_t zjni_index_bytes(size_t n, size_t E) { return (size_t)zj_index_bytes(n, E); }
 // One wave per buffer: lanes stride its entries, a wave-wide AND gives valid[i] (zj_pieces_count_kernel's shape).
 __global__ __launch_bounds__(64) void zj_index_buffers_kernel(const u64* __restrict__ first, const u64* __restrict__ size, const u64* __restrict__ content, const u64* __restrict__ result,
@@ -4277,10 +4349,7 @@ __global__ __launch_bounds__(256) void zj_index_content_kernel(const u64* __rest
 static size_t index_build_ordered(DevState* d, size_t n, const u64* d_first, const u64* d_size, const u64* d_content, const u64* d_result, size_t E, u64* d_index, hipStream_t st) {
     u64* const first = d_index; u64* const valid = d_index + n + 1; u64* const C = d_index + 2 * n + 1; u64* const U = C + E + 1;
     if (hipMemcpyAsync(first, d_first, (n + 1) * 8, hipMemcpyDeviceToDevice, st) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
-    if (n) {
-        u32 const gridW = (u32)(n < (size_t)d->numCU * 8 ? n : (size_t)d->numCU * 8);
-        hipLaunchKernelGGL(zj_index_buffers_kernel, dim3(gridW), dim3(64), 0, st, d_first, d_size, d_content, d_result, (u32)n, (u64)E, valid);
-    }
+    if (n) hipLaunchKernelGGL(zj_index_buffers_kernel, dim3(grid_cap(d, n)), dim3(64), 0, st, d_first, d_size, d_content, d_result, (u32)n, (u64)E, valid);
     hipLaunchKernelGGL(zj_index_scan_kernel, dim3(2), dim3(ZJ_INDEX_SCAN_WG), 0, st, d_size, d_content, (u64)E, C, U);
     return hipGetLastError() == hipSuccess ? 0 : ZJNI_ERR(ZJNI_ERROR_no_device);
 }
@@ -4427,40 +4496,24 @@ __global__ __launch_bounds__(64) void zj_index_edges_kernel(const ZRRec* __restr
     out[2 * i] = cout[0]; out[2 * i + 1] = cout[1];
     if (i + 1 == R) { srcA[a1] = cA[R]; dstA[a1] = dstA[a1 - 1]; srcB[fB[R]] = cA[R] + cB[R]; dstB[fB[R]] = eB[R]; }
 }
-// One wave per request, zj_range_finish_kernel with one rule more: an entry that decoded without error to another size than the index says answers 20, as does a
-// request an entry marked.  stat[8 .. 12).
+// The indexed entry's finish (zj_range_finish_body), with one rule more than the walked one: an entry that decoded without error to another size than the index
+// says answers 20, as does a request an entry marked.
+struct ZRFinishIndexed {
+    static constexpr u32 kStat = 8;
+    const ZRRec* rec; const ZIReq* ireq; const u32* bad; const u64* U;
+    __device__ u64 initial(u32 i) const { return bad[i] ? ZJ_ERR64(ZJ_E_CORRUPTION) : 0; }
+    __device__ u64 edge(u32 i, u64 v, bool last) const { return zj_index_verdict(v, last ? rec[i].fcsL : rec[i].fcsF); }
+    __device__ u64 interior(u32 i, u64 k, u64 v) const { u64 const e = ireq[i].e0 + k; return zj_index_verdict(v, U[e + 1] - U[e]); }
+};
 __global__ __launch_bounds__(64) void zj_index_finish_kernel(const u64* __restrict__ idx, u64 n, u64 E, const ZRRec* __restrict__ rec, const ZIReq* __restrict__ ireq, const u32* __restrict__ bad,
                                                              const u64* __restrict__ scan, const u64* __restrict__ resA, const u64* __restrict__ resB,
                                                              u64* __restrict__ result, u32 R, ZRCopy* __restrict__ out, u32* stat) {
-    u32 const lane = threadIdx.x;
-    const u64* const U = zj_index_view(idx, n, E).U;
-    for (u32 i = blockIdx.x; i < R; i += gridDim.x) {
-        u32 const status = rec[i].status, e = rec[i].edges, frames = rec[i].frames;
-        if (status != ZJ_RANGE_SELECTED) {
-            if (lane == 0) { result[i] = status == ZJ_RANGE_NOTHING ? 0 : ZJ_ERR64(status); atomicAdd(&stat[status == ZJ_RANGE_NOTHING ? 8 : 11], 1u); }
-            continue;
-        }
-        u64 const a0 = scan[i], m = scan[i + 1] - a0 - 1u, b0 = scan[(u64)R + 1u + i], e0 = ireq[i].e0;
-        u64 err = bad[i] ? ZJ_ERR64(ZJ_E_CORRUPTION) : 0;
-        if (!err && (e & 1u)) err = zj_index_verdict(resB[b0], rec[i].fcsF);
-        for (u64 base = 0; base < m && !err; base += 64) {
-            u64 const k = base + lane;
-            u64 const v = k < m ? zj_index_verdict(resA[a0 + k], U[e0 + k + 1] - U[e0 + k]) : 0;
-            unsigned long long const mask = __ballot(v != 0);
-            if (mask) err = __shfl(v, (int)(__ffsll((long long)mask) - 1), 64);
-        }
-        if (!err && (e & 2u)) err = zj_index_verdict(resB[b0 + (e & 1u)], rec[i].fcsL);
-        if (lane == 0) {
-            result[i] = err ? err : rec[i].hi - rec[i].lo;
-            if (err) { out[2 * (u64)i].len = 0; out[2 * (u64)i + 1].len = 0; }
-            atomicAdd(&stat[err ? 11 : 8], 1u); atomicAdd(&stat[9], frames); atomicAdd(&stat[10], zj_range_edge_count(e));
-        }
-    }
+    zj_range_finish_body(ZRFinishIndexed{rec, ireq, bad, zj_index_view(idx, n, E).U}, rec, scan, resA, resB, result, R, out, stat);
 }
 size_t zjni_decompress_index_range_batch_device(const void* d_src, const uint64_t* d_src_off, size_t n, const void* d_index, size_t E, const uint64_t* d_req,
                                                 void* d_dst, const uint64_t* d_dst_off, uint64_t* d_result, uint64_t* d_total, size_t R,
                                                 const zjni_ddict* ddict, void* stream) {
-    if (ddict && ddict->ordinal != t_dev && t_dev >= 0) return ZJNI_ERR(32);      // digested on another device
+    if (ddict && !dict_on_this_device(ddict->ordinal)) return ZJNI_ERR(32);
     DevState* d = cur_state();
     if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
     if (n > 0xFFFFFFFFull || E > 0xFFFFFFFFull || R > 0xFFFFFFFFull) return ZJNI_ERR(72);
@@ -4479,48 +4532,23 @@ size_t zjni_decompress_index_range_batch_device(const void* d_src, const uint64_
     hipLaunchKernelGGL(zj_index_request_kernel, dim3(gridR), dim3(64), 0, st, idx, (u64)n, (u64)E, (const u64*)d_src_off, (const u64*)d_req, (const u64*)d_dst_off,
                        (ZRRec*)(d->framesBuf + oRec), (ZIReq*)(d->framesBuf + oReq), (u32*)(d->framesBuf + oBad), (u64*)(d->framesBuf + oQ), (u64*)d_total, (u32)R);
     hipLaunchKernelGGL(zj_range_scan_kernel, dim3(5), dim3(1024), 0, st, (const u64*)(d->framesBuf + oQ), (u64*)(d->framesBuf + oScan), (u64*)(d->framesBuf + oTot), (u32)R);
-    // the entry's only host wait, as in the walked entry: the five totals in one copy of 40 bytes (the pipelines size their launches on the host)
-    if (hipMemcpyAsync((void*)d->framesE, d->framesBuf + oTot, 40, hipMemcpyDeviceToHost, st) != hipSuccess || hipEventRecord(d->evFramesE, st) != hipSuccess
-        || hipEventSynchronize(d->evFramesE) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
-    u64 const EA = d->framesE[0], EB = d->framesE[1], CA = d->framesE[2], CB = d->framesE[3], SB = d->framesE[4];
-    if (EA > 0xFFFFFFFFull) return ZJNI_ERR(72);
-    if (EA < R || EB > 2 * (u64)R) return ZJNI_ERR(ZJNI_ERROR_no_device);          // (every request has its closing entry and at most two edges)
-    // per entry and per run: [srcA EA + 1][dstA EA + 1][resA EA][srcB EB + 1][dstB EB + 1][resB EB][in 3R][out 2R][compact bytes CA + CB][edge scratch SB]
-    size_t const oSrcA = perReq, oDstA = oSrcA + zj_up16((EA + 1) * 8), oResA = oDstA + zj_up16((EA + 1) * 8), oSrcB = oResA + zj_up16(EA * 8 + 8),
-                 oDstB = oSrcB + zj_up16((EB + 1) * 8), oResB = oDstB + zj_up16((EB + 1) * 8), oIn = oResB + zj_up16(EB * 8 + 8), oOut = oIn + zj_up16(3 * R * sizeof(ZRCopy)),
-                 oComp = oOut + zj_up16(2 * R * sizeof(ZRCopy)), oEdge = oComp + zj_up16(CA + CB) + 16, total = oEdge + zj_up16(SB) + 16;
-    if (CA + CB < CA || total < oComp || total < SB) return ZJNI_ERR(64);
-    if ((r = frames_room(d, total, perReq, st)) != 0) return r;
+    RangePlan p;
+    if ((r = range_plan_read(d, oTot, R, perReq, st, p)) != 0) return r;
     u8* const fb = d->framesBuf;
     const ZRRec* const rec = (const ZRRec*)(fb + oRec); const ZIReq* const ireq = (const ZIReq*)(fb + oReq); u32* const bad = (u32*)(fb + oBad);
     const u64* const scan = (const u64*)(fb + oScan);
-    ZRCopy* const in = (ZRCopy*)(fb + oIn); ZRCopy* const out = (ZRCopy*)(fb + oOut);
-    u32 const gridA = (u32)((EA + ZJ_INDEX_EMIT_WG - 1u) / ZJ_INDEX_EMIT_WG);
-    if (EA > R) hipLaunchKernelGGL(zj_index_check_kernel, dim3(gridA), dim3(ZJ_INDEX_EMIT_WG), 0, st, idx, (u64)n, (u64)E, rec, ireq, scan, (u32)R, EA, bad);
-    hipLaunchKernelGGL(zj_index_emit_kernel, dim3(gridA), dim3(ZJ_INDEX_EMIT_WG), 0, st, idx, (u64)n, (u64)E, rec, ireq, (const u32*)bad, scan, (const u64*)d_dst_off, (u32)R, EA,
-                       (u64*)(fb + oSrcA), (u64*)(fb + oDstA));
-    hipLaunchKernelGGL(zj_index_edges_kernel, dim3(gridR), dim3(64), 0, st, rec, ireq, scan, (const u64*)d_dst_off, (u32)R, (u64*)(fb + oSrcA), (u64*)(fb + oDstA),
-                       (u64*)(fb + oSrcB), (u64*)(fb + oDstB), in, out);
-    u64 const tilesIn = (CA + CB + ZJ_RANGE_TILE - 1) / ZJ_RANGE_TILE, tilesOut = (SB + ZJ_RANGE_TILE - 1) / ZJ_RANGE_TILE;
-    if (tilesIn > 0x7FFFFFFFull || tilesOut > 0x7FFFFFFFull) return ZJNI_ERR(64);
-    if (tilesIn) hipLaunchKernelGGL(zj_range_gather_kernel, dim3((u32)tilesIn), dim3(256), 0, st, (const ZRCopy*)in, (u64)(3 * R), (const u8*)d_src, fb + oComp, 1u, CA + CB);
-    if (hipGetLastError() != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
-    if (EA > R && (r = decompress_chunked_ordered(fb + oComp, (const u64*)(fb + oSrcA), d_dst, (const u64*)(fb + oDstA), (u64*)(fb + oResA), (size_t)EA, ddict, stream)) != 0) return r;
-    if (EB && (r = decompress_chunked_ordered(fb + oComp, (const u64*)(fb + oSrcB), fb + oEdge, (const u64*)(fb + oDstB), (u64*)(fb + oResB), (size_t)EB, ddict, stream)) != 0) return r;
-    u32 const gridF = (u32)(R < (size_t)d->numCU * 8 ? R : (size_t)d->numCU * 8);
-    hipLaunchKernelGGL(zj_index_finish_kernel, dim3(gridF), dim3(64), 0, st, idx, (u64)n, (u64)E, rec, ireq, (const u32*)bad, scan, (const u64*)(fb + oResA), (const u64*)(fb + oResB),
-                       (u64*)d_result, (u32)R, out, d->framesStat);
-    if (tilesOut) hipLaunchKernelGGL(zj_range_gather_kernel, dim3((u32)tilesOut), dim3(256), 0, st, (const ZRCopy*)out, (u64)(2 * R), (const u8*)(fb + oEdge), (u8*)d_dst, 0u, SB);
-    return hipGetLastError() == hipSuccess ? 0 : ZJNI_ERR(ZJNI_ERROR_no_device);
+    u32 const gridA = (u32)((p.EA + ZJ_INDEX_EMIT_WG - 1u) / ZJ_INDEX_EMIT_WG);
+    if (p.EA > R) hipLaunchKernelGGL(zj_index_check_kernel, dim3(gridA), dim3(ZJ_INDEX_EMIT_WG), 0, st, idx, (u64)n, (u64)E, rec, ireq, scan, (u32)R, p.EA, bad);
+    hipLaunchKernelGGL(zj_index_emit_kernel, dim3(gridA), dim3(ZJ_INDEX_EMIT_WG), 0, st, idx, (u64)n, (u64)E, rec, ireq, (const u32*)bad, scan, (const u64*)d_dst_off, (u32)R, p.EA,
+                       (u64*)(fb + p.oSrcA), (u64*)(fb + p.oDstA));
+    hipLaunchKernelGGL(zj_index_edges_kernel, dim3(gridR), dim3(64), 0, st, rec, ireq, scan, (const u64*)d_dst_off, (u32)R, (u64*)(fb + p.oSrcA), (u64*)(fb + p.oDstA),
+                       (u64*)(fb + p.oSrcB), (u64*)(fb + p.oDstB), (ZRCopy*)(fb + p.oIn), (ZRCopy*)(fb + p.oOut));
+    if ((r = range_plan_decode(d, p, R, d_src, d_dst, ddict, stream)) != 0) return r;
+    hipLaunchKernelGGL(zj_index_finish_kernel, dim3(grid_cap(d, R)), dim3(64), 0, st, idx, (u64)n, (u64)E, rec, ireq, (const u32*)bad, scan, (const u64*)(fb + p.oResA), (const u64*)(fb + p.oResB),
+                       (u64*)d_result, (u32)R, (ZRCopy*)(fb + p.oOut), d->framesStat);
+    return range_plan_scatter(d, p, R, d_dst, st);
 }
-int zjni_last_index_range(unsigned* out4) {
-    DevState* d = cur_state();
-    if (!d || !out4) return -(int)ZJNI_ERROR_no_device;
-    u32 h[4] = {0, 0, 0, 0};
-    if (hipDeviceSynchronize() != hipSuccess || (d->framesStat && hipMemcpy(h, d->framesStat + 8, sizeof h, hipMemcpyDeviceToHost) != hipSuccess)) return -(int)ZJNI_ERROR_no_device;
-    for (int k = 0; k < 4; k++) out4[k] = h[k];
-    return 0;
-}
+int zjni_last_index_range(unsigned* out4) { return frames_stat_get(8, out4); }
 
 // ---- chunked compress ----
 size_t zjni_compressBound_chunked(size_t srcSize, size_t chunkSize) {
@@ -4582,8 +4610,7 @@ __global__ __launch_bounds__(256) void zj_chunks_verdict_kernel(const u64* __res
 }
 size_t zjni_compress_chunked_batch_device(const void* d_src, const uint64_t* d_src_off, void* d_dst, const uint64_t* d_dst_off,
                                           uint64_t* d_result, size_t n, int level, int checksum, size_t chunkSize, void* stream) {
-    if (level == 0) level = 3;                    // ZSTD_CLEVEL_DEFAULT, as ZSTD_c_compressionLevel = 0 means
-    if (!zj_level_served(level)) return ZJNI_ERR(42);
+    if (!zj_level_arg(level)) return ZJNI_ERR(42);
     if (chunkSize < 256 || chunkSize > ZJNI_BLOCKSIZE_MAX) return ZJNI_ERR(42);
     DevState* d = cur_state();
     if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
@@ -4602,7 +4629,7 @@ size_t zjni_compress_chunked_batch_device(const void* d_src, const uint64_t* d_s
     hipLaunchKernelGGL(zj_pack_offsets_kernel, dim3(1), dim3(1024), 0, st, (const u64*)(d->framesBuf + oBtot), (u64*)(d->framesBuf + oBbase), (u32)n);
     if (hipMemsetAsync(d->framesBuf + oCarry, 0, 2 * nb, st) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
     u64 E = 0;
-    if ((r = frames_read_total(d, (const u64*)(d->framesBuf + oFirst) + n, st, &E)) != 0) return r;
+    if ((r = frames_read_total(d, (const u64*)(d->framesBuf + oFirst) + n, 1, st, &E)) != 0) return r;
     if (E > 0xFFFFFFFFull) return ZJNI_ERR(72);
     if (E < n) return ZJNI_ERR(ZJNI_ERROR_no_device);
     // per slice of S entries: [srcOffS S + 1][dstOffS S + 1][resS S][packSize S][packDst S][scratch destinations: S x zjni_compressBound(chunk)]
@@ -4613,7 +4640,7 @@ size_t zjni_compress_chunked_batch_device(const void* d_src, const uint64_t* d_s
     size_t const total = oOut + zj_up16(S * bound) + 16;
     if ((r = frames_room(d, total, perBuf, st)) != 0) return r;
     u8* const fb = d->framesBuf;
-    u32 const gridW = (u32)(n < (size_t)d->numCU * 8 ? n : (size_t)d->numCU * 8);
+    u32 const gridW = grid_cap(d, n);
     for (u64 a = 0; a < E; a += S) {
         u32 const m = (u32)(E - a < S ? E - a : S);
         hipLaunchKernelGGL(zj_chunks_emit_kernel, dim3(m / 256 + 1), dim3(256), 0, st, (const u64*)d_src_off, (const u64*)(fb + oFirst), (const u64*)(fb + oBbase), (u32)n, (u64)chunkSize,
@@ -4622,8 +4649,7 @@ size_t zjni_compress_chunked_batch_device(const void* d_src, const uint64_t* d_s
         if ((r = compress_chunked_ordered(d_src, (const u64*)(fb + oSrcS), fb + oOut, (const u64*)(fb + oDstS), (u64*)(fb + oResS), m, level, checksum ? ZE_FLAG_CHECKSUM : 0u, stream)) != 0) return r;
         hipLaunchKernelGGL(zj_chunks_place_kernel, dim3(gridW), dim3(64), 0, st, (const u64*)(fb + oFirst), (const u64*)d_dst_off, (u32)n, a, m, (const u64*)(fb + oResS),
                            (u64*)(fb + oCarry), (u64*)(fb + oFerr), (u64*)(fb + oPSize), (u64*)(fb + oPDst));
-        u32 const gridP = (u32)(m < (u32)d->numCU * 8u ? m : (u32)d->numCU * 8u);
-        hipLaunchKernelGGL(zj_pack_kernel, dim3(gridP), dim3(256), 0, st, (const u8*)(fb + oOut), (const u64*)(fb + oDstS), (const u64*)(fb + oPSize), (u8*)d_dst, (const u64*)(fb + oPDst), m);
+        hipLaunchKernelGGL(zj_pack_kernel, dim3(grid_cap(d, m)), dim3(256), 0, st, (const u8*)(fb + oOut), (const u64*)(fb + oDstS), (const u64*)(fb + oPSize), (u8*)d_dst, (const u64*)(fb + oPDst), m);
     }
     hipLaunchKernelGGL(zj_chunks_verdict_kernel, dim3(gridN), dim3(256), 0, st, (const u64*)d_dst_off, (u32)n, (const u64*)(fb + oCarry), (const u64*)(fb + oFerr), (u64*)d_result);
     return hipGetLastError() == hipSuccess ? 0 : ZJNI_ERR(ZJNI_ERROR_no_device);
@@ -4676,13 +4702,10 @@ size_t zjni_compress_pieces_batch_device(const void* d_src, const uint64_t* d_sr
                                          int level, int flags, size_t chunkSize, const uint64_t* d_cut, const uint64_t* d_cut_off, const zjni_cdict* cdict,
                                          uint64_t* d_piece_first, uint64_t* d_piece_size, size_t pieceCap, void* stream) {
     if ((u32)flags & ZE_FLAG_NO_FCS) return ZJNI_ERR(42);          // a frame without a content size can be neither split nor range-read afterwards
-    if (!cdict) {
-        if (level == 0) level = 3;
-        if (!zj_level_served(level)) return ZJNI_ERR(42);
-    }
+    if (!cdict && !zj_level_arg(level)) return ZJNI_ERR(42);
     if (chunkSize < 256 || chunkSize > ZJNI_BLOCKSIZE_MAX) return ZJNI_ERR(42);
     if (d_cut && !d_cut_off) return ZJNI_ERR(42);
-    if (cdict && cdict->ordinal != t_dev && t_dev >= 0) return ZJNI_ERR(32);      // digested on another device: zjni_compress_batch_device_usingCDict's answer
+    if (cdict && !dict_on_this_device(cdict->ordinal)) return ZJNI_ERR(32);       // zjni_compress_batch_device_usingCDict's answer
     DevState* d = cur_state();
     if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
     if (n > 0xFFFFFFFFull) return ZJNI_ERR(72);
@@ -4699,17 +4722,16 @@ size_t zjni_compress_pieces_batch_device(const void* d_src, const uint64_t* d_sr
     size_t r = frames_room(d, perBuf, 0, st);
     if (r != 0) return r;
     u32 const gridN = (u32)((n + 255) / 256);
-    u32 const gridW = (u32)(n < (size_t)d->numCU * 8 ? n : (size_t)d->numCU * 8);
+    u32 const gridW = grid_cap(d, n);
     hipLaunchKernelGGL(zj_pieces_count_kernel, dim3(gridW), dim3(64), 0, st, (const u64*)d_src_off, (u32)n, (u64)chunkSize, (const u64*)d_cut, (const u64*)d_cut_off,
                        (u64*)(d->framesBuf + oCnt), (u64*)(d->framesBuf + oIdx), (u64*)(d->framesBuf + oFerr));
     hipLaunchKernelGGL(zj_pack_offsets_kernel, dim3(1), dim3(1024), 0, st, (const u64*)(d->framesBuf + oCnt), (u64*)(d->framesBuf + oFirst), (u32)n);
     hipLaunchKernelGGL(zj_pack_offsets_kernel, dim3(1), dim3(1024), 0, st, (const u64*)(d->framesBuf + oIdx), (u64*)(d->framesBuf + oIfirst), (u32)n);
     if (hipMemsetAsync(d->framesBuf + oCarry, 0, nb, st) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
     // the one host wait: E (the entries walked) and, eight bytes beside it, the entries of the caller's index — they differ by the walks of illegal lists
-    u64 E = 0, EI = 0;
-    if (hipMemcpyAsync((void*)(d->framesE + 1), (const u64*)(d->framesBuf + oIfirst) + n, 8, hipMemcpyDeviceToHost, st) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
-    if ((r = frames_read_total(d, (const u64*)(d->framesBuf + oFirst) + n, st, &E)) != 0) return r;
-    EI = d->framesE[1];
+    u64 both[2];
+    if ((r = frames_read_total(d, (const u64*)(d->framesBuf + oFirst) + n, 1, st, both, (const u64*)(d->framesBuf + oIfirst) + n)) != 0) return r;
+    u64 const E = both[0], EI = both[1];
     if (E > 0xFFFFFFFFull || EI > 0xFFFFFFFFull) return ZJNI_ERR(72);
     if (E < n || EI > E) return ZJNI_ERR(ZJNI_ERROR_no_device);
     if (d_piece_size && EI > pieceCap) return ZJNI_ERR(70);
@@ -4734,8 +4756,7 @@ size_t zjni_compress_pieces_batch_device(const void* d_src, const uint64_t* d_sr
                            (u64*)(fb + oResS), (u64*)d_piece_size, (u64)pieceCap);
         hipLaunchKernelGGL(zj_chunks_place_kernel, dim3(gridW), dim3(64), 0, st, (const u64*)(fb + oFirst), (const u64*)d_dst_off, (u32)n, a, m, (const u64*)(fb + oResS),
                            (u64*)(fb + oCarry), (u64*)(fb + oFerr), (u64*)(fb + oPSize), (u64*)(fb + oPDst));
-        u32 const gridP = (u32)(m < (u32)d->numCU * 8u ? m : (u32)d->numCU * 8u);
-        hipLaunchKernelGGL(zj_pack_kernel, dim3(gridP), dim3(256), 0, st, (const u8*)(fb + oOut), (const u64*)(fb + oDstS), (const u64*)(fb + oPSize), (u8*)d_dst, (const u64*)(fb + oPDst), m);
+        hipLaunchKernelGGL(zj_pack_kernel, dim3(grid_cap(d, m)), dim3(256), 0, st, (const u8*)(fb + oOut), (const u64*)(fb + oDstS), (const u64*)(fb + oPSize), (u8*)d_dst, (const u64*)(fb + oPDst), m);
     }
     hipLaunchKernelGGL(zj_chunks_verdict_kernel, dim3(gridN), dim3(256), 0, st, (const u64*)d_dst_off, (u32)n, (const u64*)(fb + oCarry), (const u64*)(fb + oFerr), (u64*)d_result);
     return hipGetLastError() == hipSuccess ? 0 : ZJNI_ERR(ZJNI_ERROR_no_device);
@@ -4748,25 +4769,18 @@ static size_t host_one_buffer(bool compress, void* dst, size_t dstCap, const voi
     if (srcSize > ((size_t)1 << 46) || dstCap > ((size_t)1 << 46)) return ZJNI_ERR(64);
     if ((srcSize && !src) || (dstCap && !dst)) return ZJNI_ERR(72);
     size_t const oSrc = 64, oDst = oSrc + zj_up16(srcSize), total = oDst + dstCap + 16;
-    SlotLock slotLock(d); StageSlot* const sl = slotLock.s;
-    if (!ensure_staging(sl, total)) return ZJNI_ERR(ZJNI_ERROR_unsupported);
-    hipStream_t const hst = sl->hostK;
-    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drainOnExit{hst};
-    u64* const h = (u64*)sl->hPinned;
+    StagedCall sc(d, total);
+    if (!sc.ready) return ZJNI_ERR(ZJNI_ERROR_unsupported);
+    u64* const h = sc.words();
     h[0] = 0; h[1] = srcSize; h[2] = 0; h[3] = dstCap; h[4] = 0;
-    if (srcSize) memcpy(sl->hPinned + oSrc, src, srcSize);
-    if (hipMemcpyAsync(sl->dStage, sl->hPinned, oSrc + srcSize, hipMemcpyHostToDevice, hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
-    const u64* const dOff = (const u64*)sl->dStage;
-    size_t const r = compress ? zjni_compress_chunked_batch_device(sl->dStage + oSrc, dOff, sl->dStage + oDst, dOff + 2, (u64*)sl->dStage + 4, 1, level, checksum, chunkSize, hst)
-                              : zjni_decompress_frames_batch_device(sl->dStage + oSrc, dOff, sl->dStage + oDst, dOff + 2, (u64*)sl->dStage + 4, 1, ddict, hst);
+    if (srcSize) memcpy(sc.host + oSrc, src, srcSize);
+    if (!sc.upload(oSrc + srcSize)) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    u64* const dW = (u64*)sc.dev;
+    size_t const r = compress ? zjni_compress_chunked_batch_device(sc.dev + oSrc, dW, sc.dev + oDst, dW + 2, dW + 4, 1, level, checksum, chunkSize, sc.st)
+                              : zjni_decompress_frames_batch_device(sc.dev + oSrc, dW, sc.dev + oDst, dW + 2, dW + 4, 1, ddict, sc.st);
     if (zjni_isError(r)) return r;
-    if (hipMemcpyAsync(sl->hPinned + 32, sl->dStage + 32, 8, hipMemcpyDeviceToHost, hst) != hipSuccess || hipStreamSynchronize(hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
-    size_t const res = (size_t)h[4];
-    if (zjni_isError(res) || res == 0) return res;
-    if (res > dstCap) return ZJNI_ERR(ZJNI_ERROR_no_device);
-    if (hipMemcpyAsync(sl->hPinned + oDst, sl->dStage + oDst, res, hipMemcpyDeviceToHost, hst) != hipSuccess || hipStreamSynchronize(hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
-    memcpy(dst, sl->hPinned + oDst, res);
-    return res;
+    if (!sc.fetch(4, 1)) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    return sc.payload((size_t)h[4], dst, dstCap, oDst);
 }
 size_t zjni_compress_chunked(void* dst, size_t dstCap, const void* src, size_t srcSize, int level, int checksum, size_t chunkSize) {
     return host_one_buffer(true, dst, dstCap, src, srcSize, level, checksum, chunkSize);
@@ -4788,33 +4802,26 @@ size_t zjni_compress_pieces(void* dst, size_t dstCap, const void* src, size_t sr
     if (!cut) nCut = 0;
     if (!pieceSize) pieceCap = 0;
     size_t const oSrc = 128, oCut = oSrc + zj_up16(srcSize), oPs = oCut + zj_up16(nCut * 8), oDst = oPs + zj_up16(pieceCap * 8), total = oDst + dstCap + 16;
-    SlotLock slotLock(d); StageSlot* const sl = slotLock.s;
-    if (!ensure_staging(sl, total)) return ZJNI_ERR(ZJNI_ERROR_unsupported);
-    hipStream_t const hst = sl->hostK;
-    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drainOnExit{hst};
-    u64* const h = (u64*)sl->hPinned;
+    StagedCall sc(d, total);
+    if (!sc.ready) return ZJNI_ERR(ZJNI_ERROR_unsupported);
+    u64* const h = sc.words();
     memset(h, 0, 128);
     h[1] = srcSize; h[3] = dstCap; h[6] = nCut;
-    if (srcSize) memcpy(sl->hPinned + oSrc, src, srcSize);
-    if (nCut) memcpy(sl->hPinned + oCut, cut, nCut * 8);
-    if (hipMemcpyAsync(sl->dStage, sl->hPinned, oPs, hipMemcpyHostToDevice, hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
-    u64* const dW = (u64*)sl->dStage;
-    size_t const r = zjni_compress_pieces_batch_device(sl->dStage + oSrc, dW, sl->dStage + oDst, dW + 2, dW + 4, 1, level, flags, chunkSize,
-                                                       cut ? (const u64*)(sl->dStage + oCut) : nullptr, cut ? dW + 5 : nullptr, cdict,
-                                                       dW + 8, pieceSize ? (u64*)(sl->dStage + oPs) : nullptr, pieceCap, hst);
+    if (srcSize) memcpy(sc.host + oSrc, src, srcSize);
+    if (nCut) memcpy(sc.host + oCut, cut, nCut * 8);
+    if (!sc.upload(oPs)) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    u64* const dW = (u64*)sc.dev;
+    size_t const r = zjni_compress_pieces_batch_device(sc.dev + oSrc, dW, sc.dev + oDst, dW + 2, dW + 4, 1, level, flags, chunkSize,
+                                                       cut ? (const u64*)(sc.dev + oCut) : nullptr, cut ? dW + 5 : nullptr, cdict,
+                                                       dW + 8, pieceSize ? (u64*)(sc.dev + oPs) : nullptr, pieceCap, sc.st);
     if (zjni_isError(r)) return r;
-    if (hipMemcpyAsync(sl->hPinned + 32, sl->dStage + 32, 8, hipMemcpyDeviceToHost, hst) != hipSuccess
-        || hipMemcpyAsync(sl->hPinned + 64, sl->dStage + 64, 16, hipMemcpyDeviceToHost, hst) != hipSuccess || hipStreamSynchronize(hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    if (!sc.fetch(4, 6)) return ZJNI_ERR(ZJNI_ERROR_no_device);                // the result and, in [8 .. 10), pieceFirst; the device left the words between as they were sent
     size_t const res = (size_t)h[4], E = (size_t)h[9];
     if (nPieces) *nPieces = E;
     if (zjni_isError(res)) return res;
     if (res > dstCap || (pieceSize && E > pieceCap)) return ZJNI_ERR(ZJNI_ERROR_no_device);
-    if (res && hipMemcpyAsync(sl->hPinned + oDst, sl->dStage + oDst, res, hipMemcpyDeviceToHost, hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
-    if (pieceSize && E && hipMemcpyAsync(sl->hPinned + oPs, sl->dStage + oPs, E * 8, hipMemcpyDeviceToHost, hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
-    if (hipStreamSynchronize(hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
-    if (res) memcpy(dst, sl->hPinned + oDst, res);
-    if (pieceSize && E) memcpy(pieceSize, sl->hPinned + oPs, E * 8);
-    return res;
+    // the frame's bytes and the piece sizes behind one wait
+    return sc.download({{dst, oDst, res}, {pieceSize, oPs, pieceSize ? E * 8 : 0}}) ? res : ZJNI_ERR(ZJNI_ERROR_no_device);
 }
 
 // the ranged form: [srcOff 2][dstOff 2][result 1][range 2][total 1] fill the slot's first 64 bytes; the slot is as large as the range can get, not as the buffer
@@ -4829,25 +4836,18 @@ size_t zjni_decompress_frames_range_usingDDict(void* dst, size_t dstCap, const v
     if (srcSize > ((size_t)1 << 46) || dstCap > ((size_t)1 << 46)) return ZJNI_ERR(64);
     if ((srcSize && !src) || (dstCap && !dst)) return ZJNI_ERR(72);
     size_t const oSrc = 64, oDst = oSrc + zj_up16(srcSize), all = oDst + dstCap + 16;
-    SlotLock slotLock(d); StageSlot* const sl = slotLock.s;
-    if (!ensure_staging(sl, all)) return ZJNI_ERR(ZJNI_ERROR_unsupported);
-    hipStream_t const hst = sl->hostK;
-    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drainOnExit{hst};
-    u64* const h = (u64*)sl->hPinned;
+    StagedCall sc(d, all);
+    if (!sc.ready) return ZJNI_ERR(ZJNI_ERROR_unsupported);
+    u64* const h = sc.words();
     h[0] = 0; h[1] = srcSize; h[2] = 0; h[3] = dstCap; h[4] = 0; h[5] = lo; h[6] = len; h[7] = 0;
-    if (srcSize) memcpy(sl->hPinned + oSrc, src, srcSize);
-    if (hipMemcpyAsync(sl->dStage, sl->hPinned, oSrc + srcSize, hipMemcpyHostToDevice, hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
-    u64* const dW = (u64*)sl->dStage;
-    size_t const r = zjni_decompress_frames_range_batch_device(sl->dStage + oSrc, dW, sl->dStage + oDst, dW + 2, dW + 5, dW + 4, dW + 7, 1, ddict, hst);
+    if (srcSize) memcpy(sc.host + oSrc, src, srcSize);
+    if (!sc.upload(oSrc + srcSize)) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    u64* const dW = (u64*)sc.dev;
+    size_t const r = zjni_decompress_frames_range_batch_device(sc.dev + oSrc, dW, sc.dev + oDst, dW + 2, dW + 5, dW + 4, dW + 7, 1, ddict, sc.st);
     if (zjni_isError(r)) return r;
-    if (hipMemcpyAsync(sl->hPinned + 32, sl->dStage + 32, 32, hipMemcpyDeviceToHost, hst) != hipSuccess || hipStreamSynchronize(hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
-    size_t const res = (size_t)h[4];
+    if (!sc.fetch(4, 4)) return ZJNI_ERR(ZJNI_ERROR_no_device);
     if (total) *total = h[7];
-    if (zjni_isError(res) || res == 0) return res;
-    if (res > dstCap) return ZJNI_ERR(ZJNI_ERROR_no_device);
-    if (hipMemcpyAsync(sl->hPinned + oDst, sl->dStage + oDst, res, hipMemcpyDeviceToHost, hst) != hipSuccess || hipStreamSynchronize(hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
-    memcpy(dst, sl->hPinned + oDst, res);
-    return res;
+    return sc.payload((size_t)h[4], dst, dstCap, oDst);
 }
 
 // The indexed form for one host buffer: rules 1-4 run here, on the host, with the functions the request kernel runs; only the selected entries' bytes and their slice
@@ -4879,27 +4879,20 @@ size_t zjni_decompress_index_range(void* dst, size_t dstCap, const void* src, si
     if (rec.status != ZJ_RANGE_SELECTED) return ZJNI_ERR(rec.status);
     u64 const eF = ir.e0 - (rec.edges & 1u), m = rec.frames, cLo = C[eF], bytes = C[eF + m] - cLo, uLo = U[eF], want = rec.hi - rec.lo;
     size_t const idxBytes = (size_t)zj_index_bytes(1, m), oIdx = 64, oSrc = oIdx + idxBytes, oDst = oSrc + zj_up16(bytes), all = oDst + want + 16;
-    SlotLock slotLock(d); StageSlot* const sl = slotLock.s;
-    if (!ensure_staging(sl, all)) return ZJNI_ERR(ZJNI_ERROR_unsupported);
-    hipStream_t const hst = sl->hostK;
-    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drainOnExit{hst};
-    u64* const h = (u64*)sl->hPinned;
+    StagedCall sc(d, all);
+    if (!sc.ready) return ZJNI_ERR(ZJNI_ERROR_unsupported);
+    u64* const h = sc.words();
     h[0] = 0; h[1] = bytes; h[2] = 0; h[3] = want; h[4] = 0; h[5] = 0; h[6] = rec.lo - uLo; h[7] = want;
-    u64* const hi = (u64*)(sl->hPinned + oIdx);
+    u64* const hi = (u64*)(sc.host + oIdx);
     hi[0] = 0; hi[1] = m; hi[2] = 0;
     for (u64 k = 0; k <= m; k++) { hi[3 + k] = C[eF + k] - cLo; hi[3 + m + 1 + k] = U[eF + k] - uLo; }
-    memcpy(sl->hPinned + oSrc, (const u8*)src + cLo, bytes);
-    if (hipMemcpyAsync(sl->dStage, sl->hPinned, oSrc + bytes, hipMemcpyHostToDevice, hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
-    u64* const dW = (u64*)sl->dStage;
-    size_t const r = zjni_decompress_index_range_batch_device(sl->dStage + oSrc, dW, 1, sl->dStage + oIdx, (size_t)m, dW + 5, sl->dStage + oDst, dW + 2, dW + 4, nullptr, 1, ddict, hst);
+    memcpy(sc.host + oSrc, (const u8*)src + cLo, bytes);
+    if (!sc.upload(oSrc + bytes)) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    u64* const dW = (u64*)sc.dev;
+    size_t const r = zjni_decompress_index_range_batch_device(sc.dev + oSrc, dW, 1, sc.dev + oIdx, (size_t)m, dW + 5, sc.dev + oDst, dW + 2, dW + 4, nullptr, 1, ddict, sc.st);
     if (zjni_isError(r)) return r;
-    if (hipMemcpyAsync(sl->hPinned + 32, sl->dStage + 32, 8, hipMemcpyDeviceToHost, hst) != hipSuccess || hipStreamSynchronize(hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
-    size_t const res = (size_t)h[4];
-    if (zjni_isError(res) || res == 0) return res;
-    if (res > dstCap) return ZJNI_ERR(ZJNI_ERROR_no_device);
-    if (hipMemcpyAsync(sl->hPinned + oDst, sl->dStage + oDst, res, hipMemcpyDeviceToHost, hst) != hipSuccess || hipStreamSynchronize(hst) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
-    memcpy(dst, sl->hPinned + oDst, res);
-    return res;
+    if (!sc.fetch(4, 1)) return ZJNI_ERR(ZJNI_ERROR_no_device);
+    return sc.payload((size_t)h[4], dst, dstCap, oDst);
 }
 
 // The walk on the host, no device: the arrays zjni_decompress_index_range takes, from the bytes alone, by the function both device walks run.
