@@ -255,6 +255,7 @@ size_t zjni_decompress_frames_range(void* dst, size_t dstCapacity, const void* s
 #define ZJNI_FRAME_NO_CONTENTSIZE 2
 #define ZJNI_FRAME_NO_DICTID      4
 #define ZJNI_SEQ_REPCODES         8   /* the sequence entries below only: ZSTD_c_searchForExternalRepcodes = enable */
+#define ZJNI_SEQ_NO_DELIMITERS    16  /* zjni_compress_sequences_* only: ZSTD_c_blockDelimiters = ZSTD_sf_noBlockDelimiters, the library cuts the blocks */
 size_t zjni_compress_batch_device_advanced(const void* d_src, const uint64_t* d_src_off,
                                            void* d_dst, const uint64_t* d_dst_off,
                                            uint64_t* d_result, size_t n, int level, int checksum, int hashLog, int chainLog, void* stream);
@@ -653,7 +654,25 @@ size_t zjni_test_compress_records_batch_device(const void* d_src, const uint64_t
  *     level), 201 otherwise; 0 means 3.  Where the level's row for the size is lazy or lazy2 (level 5 to 16 KiB, levels 6-8) a frame is served while its first block
  *     of 7 bytes or more is its last, a second one answers 201: those strategies weigh the previous block's sequence tables, which the entropy stage does not carry.
  *   - destinations as zjni_compress_batch_device2: every capacity gives the reference's size, bytes or dstSize_tooSmall (18 bytes for the header first).
- *   - no dictionary, no ZSTD_sf_noBlockDelimiters.
+ *   - no dictionary.
+ * With ZJNI_SEQ_NO_DELIMITERS the array is in libzstd's other format, ZSTD_sf_noBlockDelimiters (its default, and what zjni_mergeBlockDelimiters returns): no
+ * delimiters, the LIBRARY cuts the blocks by the reference's rule (ZSTD_transferSequences_noDelim, N/compress/zstd_compress.c:6744-6868), and frame i is the
+ * reference's frame for that setting, byte for byte, or its error code.  Without the bit nothing changes.
+ *   - a block aims at min(128 KiB, what is left); the sequence that straddles the edge decides where it ends: inside its literals the block ends at the edge; a
+ *     match is split only if it is longer than the block's target and its first half is at least the level's cParams.minMatch (the edge moves back when the second
+ *     half would be shorter than that), otherwise the block is shortened to end in front of the match.  Bytes the sequences do not cover are last literals, and
+ *     sequences behind the end of the source are never read.  A frame whose last block was shortened holds fewer bytes than its header says: the reference writes
+ *     it, so do these entries.
+ *   - offset == 0 is no delimiter but an offset like any other (the reference accepts it and writes a frame no decoder takes).  Repcodes are always searched, as
+ *     in the reference: ZJNI_SEQ_REPCODES is accepted and changes nothing.  Validation runs on the sequences as stored, trimmed and split; 107 in the frame's slot.
+ *   - litLength + matchLength that does not fit 32 bits, where the reference's arithmetic wraps and reads out of bounds, answers 107 if the frame reaches it.
+ *   - levels, sizes and destinations as above.  Where the level's row is lazy or lazy2 a source above 128 KiB answers 201 — a second compressed block does, as
+ *     above, and in this mode the caller cannot cut the blocks to avoid one.
+ *   - zjni_compress_sequences (one host buffer) with the bit answers 42 for dst == NULL, whatever the capacity: no frame, not even the empty one, fits in no
+ *     destination, and a null pointer there is an argument error before it is a size.  (Without the bit a null destination of capacity 0 is answered as before.)
+ *   - both offset arrays must ascend over the whole call (the slots of frame i are placed by d_seq_off[i] and d_src_off[i]): if one frame's pair descends or
+ *     passes d_seq_off[n] / d_src_off[n], EVERY frame of the call answers srcSize_wrong (72).  Scratch: 24 bytes per sequence, 40 per 64 KiB of the sources and
+ *     320 per frame; d_src_off[n] comes back in the same read as d_seq_off[n], still the one host wait.
  * d_seq_off[n + 1] counts SEQUENCES (frame i's are d_seqs[d_seq_off[i] .. d_seq_off[i + 1])).  Scratch: 20 bytes per sequence of the call from the library's
  * pool (zjni_set_scratch_limit applies; 64 when the call's records alone exceed it), sized from d_seq_off[n], which is read back once — the entry's one host wait;
  * everything else is enqueued on `stream`. */

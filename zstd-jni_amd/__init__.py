@@ -310,6 +310,13 @@ def lib():
 
 
 SEQ_REPCODES = 8       # ZJNI_SEQ_REPCODES, beside the checksum bit (1) in the flag word of the sequence entries
+SEQ_NO_DELIMITERS = 16 # ZJNI_SEQ_NO_DELIMITERS: the array has no block delimiters (ZSTD_sf_noBlockDelimiters), the library cuts the blocks
+
+
+def sequences_block_headers(src_size, n_seqs, flags):
+    """bytes of block headers a destination of the sequence entries needs beyond the compress bound: three per delimiter with explicit delimiters; without
+    them three per block the library may cut, about two blocks per 128 KiB (zj_sequences.h: (srcSize >> 16) + 8)"""
+    return 3 * ((src_size >> 16) + 8) if flags & SEQ_NO_DELIMITERS else 3 * (n_seqs + 1)
 
 
 def sequence_bound(n):
@@ -319,11 +326,12 @@ def sequence_bound(n):
 
 def compress_sequences(data, seqs, level, flags=0):
     """zjni_compress_sequences: one host buffer and its (k, 4) uint32 array of ZSTD_Sequence rows {offset, litLength, matchLength, rep} with explicit block
-    delimiters -> the frame ZSTD_compressSequences writes (flags: 1 checksum, SEQ_REPCODES).  Raises ZstdException with the reference's code otherwise."""
+    delimiters — or, with SEQ_NO_DELIMITERS, without any (what merge_block_delimiters returns) -> the frame ZSTD_compressSequences writes (flags: 1 checksum,
+    SEQ_REPCODES, SEQ_NO_DELIMITERS).  Raises ZstdException with the reference's code otherwise."""
     import numpy as np
     arr = np.ascontiguousarray(np.asarray(seqs, dtype=np.uint32).reshape(-1, 4))
     buf = bytes(data)
-    cap = lib().zjni_compressBound(len(buf)) + 64 + 3 * (len(arr) + 1)            # every delimiter may add a block header
+    cap = lib().zjni_compressBound(len(buf)) + 64 + sequences_block_headers(len(buf), len(arr), flags)      # every delimiter, or every block the library cuts, may add a block header
     dst = C.create_string_buffer(cap)
     r = lib().zjni_compress_sequences(dst, cap, arr.ctypes.data if len(arr) else None, len(arr), buf, len(buf), level, flags)
     if lib().zjni_isError(r):

@@ -5,7 +5,7 @@ torch is used only for device memory and the stream handle; all compute is in li
 """
 import torch
 
-from . import lib, ZstdException
+from . import lib, ZstdException, SEQ_NO_DELIMITERS, sequences_block_headers      # noqa: F401  (SEQ_NO_DELIMITERS: batch.compress_sequences' flag, exported here too)
 
 
 def _stream_ptr():
@@ -437,8 +437,9 @@ def pack(results, dst_blob, dst_off, out=None, out_off=None):
 def compress_sequences(src, src_off, seqs, seq_off, level, flags=0, dst=None, dst_off=None, results=None, _grid=0):
     """Enqueue zjni_compress_sequences_batch_device on the current stream: frames from the CALLER's sequences (ZSTD_compressSequences with explicit
     block delimiters).  src uint8 blob and src_off int64[n + 1] as everywhere; seqs an int32 / uint32 [k, 4] device tensor of ZSTD_Sequence rows
-    {offset, litLength, matchLength, rep}, seq_off int64[n + 1] counting rows.  flags: 1 checksum, 8 ZJNI_SEQ_REPCODES.  Without dst / dst_off the
-    destinations are sized here (compress bound plus a block header per sequence row, which reads src_off and seq_off back).  Returns
+    {offset, litLength, matchLength, rep}, seq_off int64[n + 1] counting rows.  flags: 1 checksum, 8 ZJNI_SEQ_REPCODES, 16 ZJNI_SEQ_NO_DELIMITERS (the
+    array has no delimiters and the library cuts the blocks, ZSTD_sf_noBlockDelimiters).  Without dst / dst_off the destinations are sized here (compress
+    bound plus a block header per sequence row — per block the library may cut without delimiters — which reads src_off and seq_off back).  Returns
     (dst, dst_off, results int64[n]): the frame's size, or a negative ZSTD / ZJNI error code (107: the frame's sequences are invalid).
     _grid: tests only, at most that many workgroups."""
     n = src_off.numel() - 1
@@ -449,7 +450,8 @@ def compress_sequences(src, src_off, seqs, seq_off, level, flags=0, dst=None, ds
         so, qo = src_off.cpu().tolist(), seq_off.cpu().tolist()
         caps = [0]
         for i in range(n):
-            caps.append(caps[-1] + lib().zjni_compressBound(max(so[i + 1] - so[i], 0)) + 64 + 3 * (max(qo[i + 1] - qo[i], 0) + 1))
+            size = max(so[i + 1] - so[i], 0)
+            caps.append(caps[-1] + lib().zjni_compressBound(size) + 64 + sequences_block_headers(size, max(qo[i + 1] - qo[i], 0), flags))
         dst = torch.empty(max(caps[-1], 1), dtype=torch.uint8, device=dev)
         dst_off = torch.tensor(caps, dtype=torch.int64, device=dev)
     if results is None:

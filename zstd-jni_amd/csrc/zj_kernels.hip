@@ -3790,6 +3790,7 @@ static size_t packed_call(const std::vector<u8>& image, size_t aRes, size_t all,
 // Records, literal offsets and block entries live in framesBuf — 20 bytes per sequence of the call and 4 per frame, counted as scratch (zjni_set_scratch_limit;
 // a call whose records alone exceed the limit answers 64) — whose size is the one thing the host has to know: d_seq_off[n], eight bytes read back once through
 // pinned memory, the entry's only host wait.  A frame's slice of the array is checked against that total on the device before anything of it is read.
+// Without delimiters the same read-back brings d_src_off[n] too: 24 bytes a sequence (the prefix word more), 40 bytes per 64 KiB of the batch's sources and 320 per frame.
 __global__ __launch_bounds__(64) void zj_seq_convert_kernel(const u64* __restrict__ srcOff, const ZSSeq* __restrict__ seqs, const u64* __restrict__ seqOff, u64 total,
                                                             ZESeq* __restrict__ rec, u32* __restrict__ lit, u32* __restrict__ nBlk, u32 n, u32 level, u32 flags, u32* workCounter) {
     GrpSeq<64> g;
@@ -3832,28 +3833,92 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 8))) void
         __syncthreads();
     }
 }
+// ZJNI_SEQ_NO_DELIMITERS: the same two steps with the library cutting the blocks (zj_sequences.h, "no block delimiters").  The conversion also takes a word a sequence for
+// the prefix, and frame i's slots start at zs_nd_slot_base — which places the slices apart only while both offset arrays ascend, so a frame that finds its own pair
+// descending or beyond the totals the host read raises counter word 2, and the frame loop then answers srcSize_wrong (72) for every frame of the call before it reads a slot.
+__global__ __launch_bounds__(64) void zj_seq_cut_kernel(const u64* __restrict__ srcOff, const ZSSeq* __restrict__ seqs, const u64* __restrict__ seqOff, u64 total, u64 totalSrc, u64 slots,
+                                                        u32* __restrict__ pfx, ZESeq* __restrict__ rec, u32* __restrict__ lit, u32* __restrict__ nBlk, u32 n, u32 level, u32* workCounter, u32* badOffsets) {
+    GrpSeq<64> g;
+    for (;;) {
+        u32 const i = zj_next_index(workCounter);
+        if (i >= n) break;
+        u64 const q0 = zj_uni64(seqOff[i]), q1 = zj_uni64(seqOff[i + 1]), s0 = zj_uni64(srcOff[i]), s1 = zj_uni64(srcOff[i + 1]);
+        bool const descending = q0 > q1 || q1 > total || s1 < s0 || s1 > totalSrc;
+        // One way through the body and ONE place where lane 0 alone writes, with the workgroup's barrier between it and the next index.  A lane-0 branch
+        // that `continue`s straight into zj_next_index lets the compiler send the other 63 lanes ahead on their own: their v_readfirstlane then reads
+        // lane 1's zero and they take frame 0 again — seen on the device as another frame's block count overwritten, and as a wave that never ends.
+        u32 answer = 1u;                                                                                         // 1: convert; else the word for nBlk[i]
+        if (descending || q1 - q0 > 0x7FFFFFFFull) answer = ZS_NO_FRAME;
+        else {
+            u64 const size64 = s1 - s0;
+            u32 const srcSize = size64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)size64;
+            ZEParams const p = ze_params_of(level, srcSize);
+            if (p.strategy == 0u || srcSize > ZE_MULTI_MAX) answer = 0u;                                         // the frame loop answers 201 before it looks at a slot
+            else {
+                u32 const cnt = (u32)(q1 - q0);
+                u64 const base = zs_nd_slot_base(q0, s0, i), mine = (u64)cnt + 2u * zs_nd_max_blocks(srcSize);
+                if (base + mine > slots) answer = ZS_NO_FRAME;                                                   // (cannot happen while the offsets ascend)
+                else zs_convert_nodelim(g, seqs + q0, cnt, srcSize, zs_ml_min(p), p.minMatch, zs_max_nbseq(p, srcSize), pfx + q0, rec + base, lit + base, (u32)mine, nBlk + i);
+            }
+        }
+        if (answer != 1u && threadIdx.x == 0) { nBlk[i] = answer; if (descending) atomicOr(badOffsets, 1u); }
+        __syncthreads();
+    }
+}
+// zj_encode_sequences_kernel for those slots: zs_compress_frame's no-delimiter instantiation
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 8))) void zj_encode_sequences_nodelim_kernel(const u8* __restrict__ src, const u64* __restrict__ srcOff, const u64* __restrict__ seqOff,
+                                                                 u8* __restrict__ dst, const u64* __restrict__ dstOff, u64* __restrict__ result, u32 n, u32 level, u32 flags,
+                                                                 ZESeq* rec, const u32* lit, const u32* nBlk, u32* workCounter, const u32* badOffsets, u8* scratch, u32 ldsBytes) {
+    __shared__ ZEncShared sh;
+    __shared__ ZSState st;
+    ZjProf pf; pf.start(nullptr);
+    GrpSeq<64> g;
+    if (threadIdx.x == 0) { sh.dictLoaded = 0; sh.ctDict[0] = 0; sh.ctDict[1] = 0; sh.ctDict[2] = 0; }
+    __syncthreads();
+    u8* const ws = scratch + (size_t)blockIdx.x * ZE_SCRATCH_BYTES;
+    bool const apart = ZJ_UNI(*badOffsets) == 0u;
+    for (;;) {
+        u32 const i = zj_next_index(workCounter);
+        if (i >= n) break;
+        u64 const s0 = zj_uni64(srcOff[i]), s1 = zj_uni64(srcOff[i + 1]), d0 = zj_uni64(dstOff[i]), d1 = zj_uni64(dstOff[i + 1]);
+        u32 const nb = ZJ_UNI(nBlk[i]);
+        u64 const base = (nb == ZS_NO_FRAME || nb == 0u || !apart) ? 0 : zs_nd_slot_base(zj_uni64(seqOff[i]), s0, i);
+        u64 const cap = d1 - d0;
+        u64 r;
+        if (s1 < s0 || d1 < d0 || !apart) r = ZJ_ERR64(ZJ_E_SRCSIZE_WRONG);
+        else if (s1 - s0 > ZE_MULTI_MAX) r = ZJ_ERR64(201);
+        else r = zs_compress_frame<GrpSeq<64>, true>(g, sh, st, zj_dyn_lds, src + s0, (u32)(s1 - s0), dst + d0, (u32)(cap > 0xFFFFFFFFull ? 0xFFFFFFFFull : cap), level, flags,
+                                                     rec + base, lit + base, nb, ws, pf, ldsBytes);
+        if (threadIdx.x == 0) result[i] = r;
+        __syncthreads();
+    }
+}
 static std::atomic<int> g_seq_grid(0);           // zjni_debug_sequences_grid
 int zjni_debug_sequences_grid(int grid) { return g_seq_grid.exchange(grid < 0 ? 0 : grid); }
 size_t zjni_sequenceBound(size_t srcSize) { return (size_t)zs_sequence_bound(srcSize); }
 size_t zjni_compress_sequences_batch_device(const void* d_src, const uint64_t* d_src_off, const zjni_sequence* d_seqs, const uint64_t* d_seq_off,
                                             void* d_dst, const uint64_t* d_dst_off, uint64_t* d_result, size_t n, int level, int flags, void* stream) {
     static_assert(sizeof(zjni_sequence) == 16 && sizeof(ZSSeq) == 16 && ZJNI_SEQ_REPCODES == ZS_FLAG_REPCODES && ZJNI_FRAME_CHECKSUM == ZE_FLAG_CHECKSUM, "zjni_sequence is ZSTD_Sequence");
-    if (flags & ~(ZJNI_FRAME_CHECKSUM | ZJNI_SEQ_REPCODES)) return ZJNI_ERR(42);
+    static_assert(ZJNI_SEQ_NO_DELIMITERS == ZS_FLAG_NODELIM, "the flag word");
+    if (flags & ~(ZJNI_FRAME_CHECKSUM | ZJNI_SEQ_REPCODES | ZJNI_SEQ_NO_DELIMITERS)) return ZJNI_ERR(42);
     if (!zj_level_arg(level)) return ZJNI_ERR(42);
     if (n == 0) return 0;
     if (n > 0x7FFFFFFFull) return ZJNI_ERR(72);
     if (!d_src_off || !d_seq_off || !d_dst_off || !d_result) return ZJNI_ERR(42);
+    bool const nodelim = (flags & ZJNI_SEQ_NO_DELIMITERS) != 0;
+    flags &= ZJNI_FRAME_CHECKSUM | ZJNI_SEQ_REPCODES;
     DevState* d = cur_state();
     if (!d) return ZJNI_ERR(ZJNI_ERROR_no_device);
     BatchOrder order(d, stream);
     hipStream_t st = (hipStream_t)stream;
     if (!frames_state(d)) return ZJNI_ERR(64);
-    u64 total = 0;
-    {   size_t const e = frames_read_total(d, (const u64*)d_seq_off + n, 1, st, &total); if (e) return e; }
-    if (total > ((u64)1 << 40)) return ZJNI_ERR(64);
+    u64 totals[2] = {0, 0};                                                          // d_seq_off[n], and without delimiters d_src_off[n]: the bound on the blocks needs the batch's bytes
+    {   size_t const e = frames_read_total(d, (const u64*)d_seq_off + n, 1, st, totals, nodelim ? (const u64*)d_src_off + n : nullptr); if (e) return e; }
+    u64 const total = totals[0], totalSrc = totals[1];
+    if (total > ((u64)1 << 40) || totalSrc > ((u64)1 << 40)) return ZJNI_ERR(64);
     if (total && !d_seqs) return ZJNI_ERR(42);
-    size_t const slots = (size_t)total + n;
-    size_t const offNblk = 64, offLit = offNblk + zj_up16(n * 4), offRec = offLit + zj_up16(slots * 4), need = offRec + slots * 16;
+    size_t const slots = nodelim ? (size_t)zs_nd_slots(total, totalSrc, n) : (size_t)total + n;
+    size_t const offNblk = 64, offLit = offNblk + zj_up16(n * 4), offRec = offLit + zj_up16(slots * 4), offPfx = offRec + slots * 16, need = offPfx + (nodelim ? (size_t)total * 4 : 0);
     {   size_t const e = frames_room(d, need, 0, st); if (e) return e; }
     u32* const ctr = (u32*)d->framesBuf;
     if (hipMemsetAsync(ctr, 0, 64, st) != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
@@ -3870,6 +3935,14 @@ size_t zjni_compress_sequences_batch_device(const void* d_src, const uint64_t* d
     u32 const lw = zs_level_word(level);
     ZESeq* const rec = (ZESeq*)(d->framesBuf + offRec); u32* const lit = (u32*)(d->framesBuf + offLit); u32* const nBlk = (u32*)(d->framesBuf + offNblk);
     size_t convGrid = grid_cap(d, n); if (want > 0 && (size_t)want < convGrid) convGrid = (size_t)want;
+    if (nodelim) {
+        hipLaunchKernelGGL(zj_seq_cut_kernel, dim3((u32)convGrid), dim3(64), 0, st, (const u64*)d_src_off, (const ZSSeq*)d_seqs, (const u64*)d_seq_off, total, totalSrc, (u64)slots,
+                           (u32*)(d->framesBuf + offPfx), rec, lit, nBlk, (u32)n, lw, ctr, ctr + 2);
+        if (hipGetLastError() != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
+        hipLaunchKernelGGL(zj_encode_sequences_nodelim_kernel, dim3((u32)grid), dim3(64), sizeof(ZEEntropy), st, (const u8*)d_src, (const u64*)d_src_off, (const u64*)d_seq_off, (u8*)d_dst,
+                           (const u64*)d_dst_off, (u64*)d_result, (u32)n, lw, (u32)flags, rec, (const u32*)lit, (const u32*)nBlk, ctr + 1, (const u32*)(ctr + 2), d->encScratch, (u32)sizeof(ZEEntropy));
+        return hipGetLastError() == hipSuccess ? 0 : ZJNI_ERR(ZJNI_ERROR_no_device);
+    }
     hipLaunchKernelGGL(zj_seq_convert_kernel, dim3((u32)convGrid), dim3(64), 0, st, (const u64*)d_src_off, (const ZSSeq*)d_seqs, (const u64*)d_seq_off, total, rec, lit, nBlk, (u32)n, lw, (u32)flags, ctr);
     if (hipGetLastError() != hipSuccess) return ZJNI_ERR(ZJNI_ERROR_no_device);
     hipLaunchKernelGGL(zj_encode_sequences_kernel, dim3((u32)grid), dim3(64), sizeof(ZEEntropy), st, (const u8*)d_src, (const u64*)d_src_off, (const u64*)d_seq_off, (u8*)d_dst,
@@ -3879,7 +3952,7 @@ size_t zjni_compress_sequences_batch_device(const void* d_src, const uint64_t* d
 // Host arrays: sources, sequence arrays and destinations go through one device buffer of the call's own (packed on the host, one copy each way).  Synchronous.
 size_t zjni_compress_sequences_batch(const void* const* src, const size_t* srcSize, const zjni_sequence* const* seqs, const size_t* nSeqs,
                                      void* const* dst, const size_t* dstCap, size_t* result, size_t n, int level, int flags) {
-    if (flags & ~(ZJNI_FRAME_CHECKSUM | ZJNI_SEQ_REPCODES)) return ZJNI_ERR(42);
+    if (flags & ~(ZJNI_FRAME_CHECKSUM | ZJNI_SEQ_REPCODES | ZJNI_SEQ_NO_DELIMITERS)) return ZJNI_ERR(42);
     if (!zj_level_arg(level)) return ZJNI_ERR(42);
     if (n == 0) return 0;
     if (n > 0x7FFFFFFFull) return ZJNI_ERR(72);
@@ -3915,6 +3988,7 @@ size_t zjni_compress_sequences_batch(const void* const* src, const size_t* srcSi
     return 0;
 }
 size_t zjni_compress_sequences(void* dst, size_t dstCapacity, const zjni_sequence* seqs, size_t nSeqs, const void* src, size_t srcSize, int level, int flags) {
+    if ((flags & ZJNI_SEQ_NO_DELIMITERS) && !dst) return ZJNI_ERR(42);      // the new mode's one-buffer form wants a destination: no frame fits in none (header)
     size_t res = 0; const void* s = src; void* dd = dst; const zjni_sequence* q = seqs;
     size_t const r = zjni_compress_sequences_batch(&s, &srcSize, &q, &nSeqs, &dd, &dstCapacity, &res, 1, level, flags);
     return zjni_isError(r) ? r : res;

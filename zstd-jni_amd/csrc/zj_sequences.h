@@ -26,6 +26,39 @@
 // Strategies from lazy upward (the rows of level 5 to 16 KiB and of levels 6-8) choose the sequence tables' modes by estimated cost with the previous
 // block's tables as a candidate (zstd_compress_sequences.c:196-222), which the entropy stage does not carry: their frames are served
 // while the first block is the last one, a second block answers 201.
+//
+// ---- ZSTD_sf_noBlockDelimiters (ZJNI_SEQ_NO_DELIMITERS) ----
+// The array has no delimiters and the library cuts the blocks: ZSTD_transferSequences_noDelim (:6744-6868) under determine_blockSize
+// (:6918-6927) and the block loop (:6969-7057).  zs_convert_nodelim is that rule for one frame, a wave:
+//   prefix   tiles of a wave give every sequence its end in the uncut stream, P[i] (4 bytes a sequence of scratch).  A length counts as at most
+//            ZS_ND_LEN_CAP and positions saturate at ZS_POS_CAP, both beyond any served source, so every P below a block edge is exact.  The pass stops
+//            with the tile that reaches the end of the source: sequences behind it are never read (nor does the reference read them).
+//   cut      the one serial chain, a step a BLOCK.  A block aims at T = min(128 KiB, remaining) and lastBlock = (T == remaining) is taken before
+//            the transfer may shorten it (:6972-6975).  With the block starting `sp` bytes into sequence idx at source position `at`, the edge is
+//            E = at + T and J the first sequence with P[J] >= E (bisection).  P[J] == E: J ends the block.  No J: the sequences ran out, the rest are
+//            last literals (:6775).  Else the edge lies in J: in its literals (:6826-6829) the block ends at E; in its match (:6799-6825) the match is
+//            split if matchLength > T and the first half >= cParams.minMatch (the row's own, not the validator's 3 / 4), the edge moving back if the
+//            second half would be under minMatch — otherwise the block is shortened to end in front of the match.
+//   emit     lanes over the block's sequences write records, literal offsets and the block entry in the slot layout above; the first sequence is
+//            trimmed by `sp`, a split last one stored as its first half (the second opens the next block with litLength 0).  Every lane validates
+//            its STORED sequence with the position behind it (:6837-6844).  Records leave with the raw offBase and ZS_SOFT: repcodes are always
+//            searched in this mode (:6762-6763, :6831-6835), so the frame loop runs zs_resolve_block whatever the flag word says.  offset == 0 is
+//            no delimiter here but offBase 3, as in the reference, which accepts it and writes an undecodable frame.
+// Three corners of the reference, restated or fenced:
+//   * a last block under 7 bytes that the transfer shortened is written raw WITH the last-block bit and the loop goes on (:6989-6998 `continue`s
+//     past :7047): the frame holds blocks behind its "last" one.  So does this.
+//   * a block that starts AT a match with fewer than minMatch bytes of source left consumes nothing (bytesAdjustment == blockSize): the reference
+//     writes empty raw blocks until the destination is full and answers dstSize_tooSmall.  ZS_STUCK: the frame loop answers that at once.
+//   * litLength + matchLength beyond 32 bits, and a block that starts INSIDE a match with fewer than minMatch bytes left (iend < istart), are
+//     undefined in the reference; a frame that reaches either answers 107.
+// Blocks per frame.  A block without the last-block bit is full (T bytes, or T less an adjustment under minMatch <= 7) or was shortened because a
+// match M straddles its edge E.  The block behind a shortened one starts at M, and M's first half there is its whole target >= minMatch, so that
+// block is not shortened at M: it holds all of M (and ends behind E) or is full.  Two consecutive blocks without the bit therefore cover more
+// than 128 KiB - 7 bytes: at most 2 * (srcSize / 131066) + 1 of them, which is <= (srcSize >> 16) + 2 up to ZE_MULTI_MAX.  Blocks WITH the bit
+// behind the first such (the first corner) are each under 7 bytes and followed by a split, a stuck or an undefined block: a handful.
+// zs_nd_max_blocks = (srcSize >> 16) + 8; a block brings one entry slot and at most one record more than the array has (the second half of a
+// split), so frame i owns cnt + 2 * zs_nd_max_blocks slots from zs_nd_slot_base.  Every slot index is checked against that slice regardless, and
+// a frame that would leave it answers 107.
 #pragma once
 #include "zj_encode.h"
 
@@ -37,6 +70,10 @@ struct ZSSeq { u32 offset, litLength, matchLength, rep; };           // == ZSTD_
 #define ZS_LEN_CAP (1u << 18)      /* a length above a block's size is counted as this much: the block is invalid either way */
 #define ZS_POS_CAP (1u << 30)      /* running positions saturate here, far beyond any served source */
 #define ZS_NO_FRAME 0xFFFFFFFFu    /* per-frame delimiter count: the frame's slice of the sequence array is not one */
+#define ZS_FLAG_NODELIM 16u        /* ZSTD_c_blockDelimiters = ZSTD_sf_noBlockDelimiters (ZJNI_SEQ_NO_DELIMITERS) */
+#define ZS_LAST 0x10000000u        /* no-delimiter block entry: lastBlock of :6975, taken before the transfer shortened the block */
+#define ZS_STUCK 0x20000000u       /* no-delimiter block entry: the transfer consumed nothing and never will (header) */
+#define ZS_ND_LEN_CAP (1u << 24)   /* no-delimiter prefix: a sequence counts as at most this much, eight times ZE_MULTI_MAX; a tile's sum stays below 2^31 */
 
 // the group of the sequence entries: ze_compress_t's own instantiation, with ZSTD_compressSequences' RLE rule (ZEExtSeq)
 template <int W_> struct GrpSeq : Grp<W_> {};
@@ -138,6 +175,112 @@ ZJ_DEV void zs_convert(const G& g, const ZSSeq* in, u32 cnt, u32 srcSize, u32 ml
     GRP_SERIAL(g) { *nBlocksOut = nBlocks; }
 }
 
+// ---- no block delimiters (header) ----
+ZJ_HD u32 zs_nd_max_blocks(u32 srcSize) { return (srcSize >> 16) + 8u; }
+// frame i's first slot: its sequences' offset plus what the frames in front of it may add.  (s1 >> 16) - (s0 >> 16) >= (s1 - s0) >> 16, so
+// consecutive slices do not overlap while the offsets ascend.
+ZJ_HD u64 zs_nd_slot_base(u64 q0, u64 s0, u64 i) { return q0 + 2u * (s0 >> 16) + 16u * i; }
+ZJ_HD u64 zs_nd_slots(u64 totalSeqs, u64 totalSrc, u64 n) { return totalSeqs + 2u * (totalSrc >> 16) + 16u * n; }
+
+// One frame's ZSTD_Sequence[cnt] without delimiters -> records, literal offsets and block entries in the frame's `slots` slots.  minMatch: the row's
+// cParams.minMatch (the split rule); mlMin, maxNbSeq as zs_convert.  pfx: cnt words of scratch.  *nBlocksOut: the entries written, or ZS_NO_FRAME
+// when the frame left its budget of blocks or slots (107).
+template <class G>
+ZJ_DEV void zs_convert_nodelim(const G& g, const ZSSeq* in, u32 cnt, u32 srcSize, u32 mlMin, u32 minMatch, u32 maxNbSeq, u32* pfx, ZESeq* rec, u32* lit, u32 slots, u32* nBlocksOut) {
+    u32 const lane = g.lane(), lastLane = (u32)G::W - 1u;
+    // prefix: P[i], the end of sequence i in the uncut stream
+    u32 lim = 0, wrapAt = 0xFFFFFFFFu;               // sequences placed; the first one whose lengths do not fit 32 bits
+    {   u32 pos = 0;
+        for (u32 t = 0; t < cnt && pos < srcSize; t += (u32)G::W) {
+            u32 const idx = t + lane;
+            bool const in_ = idx < cnt;
+            u32 ll = 0, ml = 0;
+            if (in_) { ZSSeq const s = in[idx]; ll = s.litLength; ml = s.matchLength; }
+            u64 const sum = (u64)ll + ml;
+            u32 const len = sum > ZS_ND_LEN_CAP ? ZS_ND_LEN_CAP : (u32)sum;
+            u32 const eIn = zs_scan_incl(g, len);
+            if (in_) pfx[idx] = zj_min(pos + eIn, ZS_POS_CAP);
+            u64 const wmask = grp_ballot(g, in_ && sum > 0xFFFFFFFFull);
+            if (wmask && wrapAt == 0xFFFFFFFFu) wrapAt = t + (u32)__builtin_ctzll(wmask);
+            pos = zj_min(pos + ZJ_UNI(zs_shfl(g, eIn, lastLane)), ZS_POS_CAP);
+            lim = zj_min(t + (u32)G::W, cnt);
+        }
+    }
+    zj_mem_order();
+    g.sync();
+    // cut and emit, a block a step; everything but the record lanes is wave-uniform
+    u32 const maxBlocks = zs_nd_max_blocks(srcSize);
+    u32 idx = 0, sp = 0, at = 0, slot = 0, nBlocks = 0;
+    while (at < srcSize) {
+        if (nBlocks == maxBlocks) { nBlocks = ZS_NO_FRAME; break; }
+        u32 const remaining = srcSize - at, T = zj_min((u32)ZE_BLOCK_MAX, remaining), E = at + T;
+        u32 const lastBit = T == remaining ? 1u : 0u;
+        u32 lo = idx, hi = lim;                      // J: the first sequence from idx on that ends at or behind the edge, lim if none does
+        while (lo < hi) { u32 const mid = lo + ((hi - lo) >> 1); if (ZJ_UNI(pfx[mid]) >= E) hi = mid; else lo = mid + 1u; }
+        u32 const J = lo;
+        u32 endRec = lim, nextIdx = lim, nextSp = sp, size = T, splitLl = 0, splitMl = 0;
+        bool split = false, bad = false, stuck = false;
+        if (J < lim) {
+            if (ZJ_UNI(pfx[J]) == E) { endRec = J + 1u; nextIdx = J + 1u; nextSp = 0; }      // :6783-6793, and endPosInSequence == 0 ends the loop (:6775)
+            else {
+                u32 const sll = ZJ_UNI(in[J].litLength), sml = ZJ_UNI(in[J].matchLength);
+                u32 const A = J ? ZJ_UNI(pfx[J - 1u]) : 0u;                              // < E: exact
+                u32 const spJ = J == idx ? sp : 0u;
+                u32 endRel = E - A;                                                      // endPosInSequence
+                endRec = J; nextIdx = J;
+                if (endRel > sll) {                                                      // :6799
+                    u32 const llT = spJ >= sll ? 0u : sll - spJ;
+                    u32 firstHalf = endRel - spJ - llT;
+                    if (sml > T && firstHalf >= minMatch) {                              // :6803
+                        u32 const second = sml + sll - endRel;
+                        if (second < minMatch) { u32 const adj = minMatch - second; endRel -= adj; firstHalf -= adj; size = T - adj; }
+                        split = true; splitLl = llT; splitMl = firstHalf; endRec = J + 1u; nextSp = endRel;
+                    } else if (spJ > sll) bad = true;                                    // iend < istart in the reference: undefined there (header)
+                    else { size = A + sll - at; nextSp = sll; stuck = size == 0u; }     // :6822-6824
+                } else nextSp = endRel;                                                  // :6826-6829
+            }
+        }
+        u32 const nb = endRec - idx;
+        if ((J < lim ? J : lim - 1u) >= wrapAt && lim) bad = true;                        // a sequence the reference's 32-bit arithmetic cannot hold was reached
+        if ((u64)slot + 1u + nb > slots) { nBlocks = ZS_NO_FRAME; break; }
+        u32 litCarry = 0; bool soft = false;
+        for (u32 t = 0; t < nb; t += (u32)G::W) {
+            u32 const k = t + lane, j = idx + k;
+            bool const in_ = k < nb;
+            u32 off = 1, ll = 0, ml = 0, start = at;
+            if (in_) {
+                ZSSeq const s = in[j]; off = s.offset; ll = s.litLength; ml = s.matchLength;
+                if (j == idx) { if (sp >= ll) { ml -= sp - ll; ll = 0; } else ll -= sp; }            // :6784-6790
+                else start = pfx[j - 1u];
+                if (split && j == J) { ll = splitLl; ml = splitMl; }                                 // :6801, :6812
+            }
+            u32 const llc = zj_min(ll, ZS_ND_LEN_CAP);
+            u32 const lIn = zs_scan_incl(g, llc);
+            u32 const e = start + ll + ml;                                                           // posInSrc behind the stored sequence (:6838)
+            u32 const offBase = off + 3u;
+            bool const sft = in_ && (u64)offBase > (u64)e + 3u;                                      // :6615 — unless the walk makes it a repcode
+            bool const hard = in_ && (ml < mlMin || offBase == 0u || k >= maxNbSeq);                 // :6617, :6844
+            if (grp_ballot(g, hard)) bad = true;
+            if (grp_ballot(g, sft)) soft = true;
+            if (in_) {
+                ZESeq r; r.ll = ll; r.ml = ml; r.off = offBase; r.pos = ((start - at) & 0x3FFFFFFFu) | (sft ? ZS_SOFT : 0u);
+                rec[slot + 1u + k] = r; lit[slot + 1u + k] = litCarry + lIn - llc;
+            }
+            litCarry = zj_min(litCarry + ZJ_UNI(zs_shfl(g, lIn, lastLane)), ZS_POS_CAP);
+        }
+        // last literals: from the end of the last stored sequence to the block's end (:6857-6865)
+        u32 const seqEnd = nb == 0u ? at : (split ? at + size : ZJ_UNI(pfx[endRec - 1u]));
+        u32 const lastLL = at + size - seqEnd;
+        GRP_SERIAL(g) {
+            ZESeq r; r.ll = nb; r.ml = litCarry + lastLL; r.off = lastLL; r.pos = at;
+            rec[slot] = r; lit[slot] = size | (lastBit ? ZS_LAST : 0u) | (stuck ? ZS_STUCK : 0u) | (bad ? ZS_BAD : 0u) | (soft ? ZS_SOFT : 0u);
+        }
+        nBlocks++; slot += nb + 1u; at += size; idx = nextIdx; sp = nextSp;
+        if (bad || stuck || (lastBit && (size >= 7u || at == srcSize))) break;             // :7047 — a last block under 7 bytes does not end the loop (:6998)
+    }
+    GRP_SERIAL(g) { *nBlocksOut = nBlocks; }
+}
+
 // what the frame loop carries besides ZEncShared
 struct ZSState { u32 rep[3], nextRep[3], fail; };
 
@@ -167,7 +310,9 @@ ZJ_DEV void zs_resolve_block(ZSState& st, ZESeq* seqs, u32 nb) {
 
 // The frame: ZSTD_compressSequences (:7063-7110) around ZSTD_compressSequences_internal (:6944-7061).
 // rec / lit: the frame's slots as zs_convert left them, nBlocks its delimiters.  Returns the frame's size or ZJ_ERR64(code).
-template <class G>
+// ND: the slots are zs_convert_nodelim's — the entry carries lastBlock, the frame ends on that bit even when bytes are left, and the repcode
+// walk always runs.  A compile-time property: the explicit instantiation is the code it was.
+template <class G, bool ND = false>
 ZJ_DEV u64 zs_compress_frame(const G& g, ZEncShared& sh, ZSState& st, u8* lds, const u8* src, u32 srcSize, u8* dst, u32 dstCap, u32 level, u32 flags,
                              ZESeq* rec, const u32* lit, u32 nBlocks, u8* ws, ZjProf& pf, u32 ldsBytes) {
     ZEParams const p = ze_params_of(level, srcSize);                 // the level's row for the pledged size (ZSTD_CCtx_init_compressStream2 with ZSTD_e_end, :7074)
@@ -200,14 +345,15 @@ ZJ_DEV u64 zs_compress_frame(const G& g, ZEncShared& sh, ZSState& st, u8* lds, c
         // determine_blockSize and the transfer's checks (:6929-6935, :6684-6695, :6728); a block in front of a bad one has been written by
         // now and could have run out of room first — the order the reference meets its errors in
         if (word & ZS_BAD) return ZJ_ERR64(ZS_E_SEQUENCES);
+        if (ND && (word & ZS_STUCK)) return ZJ_ERR64(ZJ_E_DSTSIZE_TOO_SMALL);          // empty raw blocks until the destination is full (header)
         ZESeq* const seqs = rec + slot + 1u;
-        if (flags & ZS_FLAG_REPCODES) {
+        if (ND || (flags & ZS_FLAG_REPCODES)) {
             GRP_SERIAL(g) { zs_resolve_block(st, seqs, nb); }
             zj_mem_order();
             g.sync();
             if (ZJ_UNI(st.fail)) return ZJ_ERR64(ZS_E_SEQUENCES);
         }
-        u32 const lastBlock = (at + size == srcSize) ? 1u : 0u;      // :6975; sequences behind such a block are never looked at (:7047)
+        u32 const lastBlock = ND ? ((word & ZS_LAST) ? 1u : 0u) : ((at + size == srcSize) ? 1u : 0u);      // :6975; sequences behind such a block are never looked at (:7047)
         u32 const room = dstCap - pos;
         if (size < 7u) {                                             // :6989: MIN_CBLOCK_SIZE + ZSTD_blockHeaderSize + 1 + 1 — raw, and the frame's "first block" stays open (the `continue` skips :7054)
             if (size + 3u > room) return ZJ_ERR64(ZJ_E_DSTSIZE_TOO_SMALL);           // ZSTD_noCompressBlock
@@ -224,7 +370,7 @@ ZJ_DEV u64 zs_compress_frame(const G& g, ZEncShared& sh, ZSState& st, u8* lds, c
             g.sync();
             // :7031-7037: only a block emitted compressed confirms its repcodes (and, inside ze_compress_t, its Huffman table).  The
             // offcode table's valid -> check step of :7035 needs a dictionary's table to be valid in the first place: there is none here.
-            if ((flags & ZS_FLAG_REPCODES) && ((ZJ_UNI((u32)dst[pos]) >> 1) & 3u) == 2u) {
+            if ((ND || (flags & ZS_FLAG_REPCODES)) && ((ZJ_UNI((u32)dst[pos]) >> 1) & 3u) == 2u) {
                 GRP_SERIAL(g) { st.rep[0] = st.nextRep[0]; st.rep[1] = st.nextRep[1]; st.rep[2] = st.nextRep[2]; }
                 g.sync();
             }
@@ -232,7 +378,7 @@ ZJ_DEV u64 zs_compress_frame(const G& g, ZEncShared& sh, ZSState& st, u8* lds, c
             if (!lastBlock) isFirst = 0;                             // :7054
         }
         at += size; slot += nb + 1u;
-        if (lastBlock) closed = true;
+        if (ND ? (lastBlock && (size >= 7u || at == srcSize)) : lastBlock != 0u) closed = true;      // (ND: the raw path `continue`s past :7047)
     }
     if (!closed) return ZJ_ERR64(ZS_E_SEQUENCES);                    // :6913 / :6695: the source goes on and no delimiter is left
     if (tail) {
