@@ -376,6 +376,7 @@ extern "C" unsigned long long emu_compress_records(const unsigned char* src, uns
     u8* fs = (u8*)malloc(ZE_FRAME_STRIDE(maxSrc)); memset(fs, 0xC3, ZE_FRAME_STRIDE(maxSrc));
     ZESeq* const seqs = (ZESeq*)fs; u32* const litOff = (u32*)(fs + (size_t)ZE_FRAME_MAXSEQ(maxSrc) * 16u);
     u32 lit = 0;
+    for (u32 i = 0; i < nbSeq; i++) if (rec[4 * i + 2] >= (1u << 24)) { free(fs); return ZJ_ERR64(42); }      // THIS WRAPPER's guard, not a check the library makes: the stage keeps a value's code in the record's top byte and relies on offBase < 2^24, which the entries' window validation (zs_convert's offFail) and the match finders' window guarantee on the device
     for (u32 i = 0; i < nbSeq; i++) { ZESeq s; s.ll = rec[4 * i]; s.ml = rec[4 * i + 1]; s.off = rec[4 * i + 2]; s.pos = rec[4 * i + 3]; seqs[i] = s; litOff[i] = lit; lit += s.ll; }
     u32 meta[3] = { nbSeq, litSize, lastLL };
     ZEPre pre; pre.seqs = seqs; pre.litOff = litOff; pre.meta = meta;

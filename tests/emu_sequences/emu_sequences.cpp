@@ -43,3 +43,15 @@ extern "C" unsigned long long emu_compress_sequences(const unsigned char* src, u
     free(s); free(q); free(d); free(rec); free(lit);
     return r;
 }
+
+// The frame loop's answer for a slot the conversion kernel marked ZS_NO_FRAME (the frame's pair of sequence offsets descends): no slot is read.
+extern "C" unsigned long long emu_compress_no_frame(const unsigned char* src, unsigned srcSize, unsigned char* dst, unsigned dstCap, int level, unsigned flags) {
+    GrpSeq<1> g;
+    EmuSeqWg& wg = emu_seq_wg();
+    u8* const s = (u8*)malloc(srcSize ? srcSize : 1); if (srcSize) memcpy(s, src, srcSize);
+    u8* const d = (u8*)malloc(dstCap ? dstCap : 1);
+    ZjProf pf; pf.start(nullptr);
+    u64 const r = zs_compress_frame(g, *wg.sh, *wg.st, wg.lds, s, srcSize, d, dstCap, zs_level_word(level), flags & (ZE_FLAG_CHECKSUM | ZS_FLAG_REPCODES), (ZESeq*)nullptr, (const u32*)nullptr, ZS_NO_FRAME, wg.ws, pf, 160u * 1024u);
+    free(s); free(d);
+    return r;
+}

@@ -66,12 +66,14 @@ def _literals(rnd, n, kind):
     return raw if kind == "raw" else raw.translate(_TEXT)
 
 
-def build(blocks, level=3, checksum=False, window_log=0, dictionary=None, literals="text", seed=1, ext_rep=True):
+def build(blocks, level=3, checksum=False, window_log=0, dictionary=None, literals="text", seed=1, ext_rep=True, decodable=True):
     """blocks = [([(ll, ml, offset), ...], trailing literals), ...] -> (frame, content, shape).  The content is what the triples
     mean: ll literal bytes, then ml bytes each equal to the byte `offset` positions back (copied in runs of at most `offset`
     bytes, which is the same as byte by byte), the dictionary's content in front.  literals: "text" eight letters (Huffman),
     "raw" random bytes, "rle" one value; a bytes object: the frame's literal bytes themselves, taken run after run (tests/seqrecords.py
-    chooses histograms with it).  ext_rep=False: searchForExternalRepcodes off — every offset is stored as offset + 3, no repcode is written."""
+    chooses histograms with it).  ext_rep=False: searchForExternalRepcodes off — every offset is stored as offset + 3, no repcode is written.
+    decodable=False: offsets may reach in front of the content (tests/branch_cases.py "wide-codes": an offset code no window allows) — validateSequences is off, the
+    reference writes the frame all the same and no decoder takes it; the bytes of such a match are more literal-kind bytes, which no one reads."""
     from oracle import ref
     assert level <= 9                                  # from level 16 on the library may re-split blocks
     L = _lib()
@@ -95,9 +97,12 @@ def build(blocks, level=3, checksum=False, window_log=0, dictionary=None, litera
     for seqs, tail in blocks:
         for ll, ml, off in seqs:
             out += lits(ll)
-            assert ml >= 3 and 1 <= off <= len(out), (ll, ml, off, len(out))
+            assert ml >= 3 and 1 <= off and (off <= len(out) or not decodable), (ll, ml, off, len(out))
             arr[i].offset, arr[i].litLength, arr[i].matchLength = off, ll, ml
             i += 1
+            if off > len(out):
+                out += _literals(rnd, ml, "text")
+                ml = 0
             while ml:
                 n = min(ml, off)
                 s = len(out) - off
@@ -110,7 +115,7 @@ def build(blocks, level=3, checksum=False, window_log=0, dictionary=None, litera
     cctx = L.ZSTD_createCCtx()
     try:
         params = [(100, level), (201, int(checksum)), (105, 3),                  # compressionLevel, checksumFlag, minMatch
-                  (1008, 1), (1009, 1),                                          # blockDelimiters: explicit; validateSequences
+                  (1008, 1), (1009, int(decodable)),                             # blockDelimiters: explicit; validateSequences
                   (1016, 1 if ext_rep else 2)]                                   # searchForExternalRepcodes: on (below level 10 "auto" means off: no repcode would be written); 2 = off
         if window_log:
             params.append((101, window_log))
@@ -124,8 +129,9 @@ def build(blocks, level=3, checksum=False, window_log=0, dictionary=None, litera
         frame = dst.raw[:r]
     finally:
         L.ZSTD_freeCCtx(cctx)
-    back = ref.decompress_using_dict(frame, d.raw, len(content)) if d else ref.decompress(frame, len(content))
-    assert back == content, "the reference does not confirm the frame"
+    if decodable:
+        back = ref.decompress_using_dict(frame, d.raw, len(content)) if d else ref.decompress(frame, len(content))
+        assert back == content, "the reference does not confirm the frame"
     return frame, content, walk(frame)
 
 

@@ -7,7 +7,7 @@ block placement) therefore meets quantities no finder emits on request: literal 
 compressed size passes through srcSize - minGain.
 
 records()           -> the repcode model (ZSTD_finalizeOffBase / ZSTD_updateRep); self-checking: a mistake in it makes every frame differ
-families G L S M W R B U -> lists of Case (one block each); every case runs at levels 1 and 3, and at 4 and 5 when it fits in 16 KiB
+families G L S M W R B U N -> lists of Case (one block each); every case runs at levels 1 and 3, and at 4 and 5 when it fits in 16 KiB
 families P, RB      -> lists of MCase: frames of several caller-cut blocks (previous tables, repcodes behind raw and RLE blocks), levels 1 and 3
 bound_U()           -> the pipelined parse's upper bound of a block's size and its premises, restated from the records
 TEST INFRASTRUCTURE — used by tests/test_emu_seqrecords.py (CPU) and tests/test_gpu_seqrecords.py (GPU)."""
@@ -420,6 +420,50 @@ def family_u():
     return out
 
 
+def _code_values(ll_codes, ml_codes):
+    """one sequence per pair of codes: the smallest literal length and match length of each code, offsets 1 .. 9 within what lies before them"""
+    seqs, pos = [], 0
+    for i, (l, m) in enumerate(zip(ll_codes, ml_codes)):
+        ll, ml = l if l < 16 else S.LL_BASE[l - 16], m + 3 if m < 32 else S.ML_BASE[m - 32]
+        assert pos + ll >= 1, "a frame's first sequence needs a literal"
+        seqs.append((ll, ml, min(1 + (5 * i) % 9, pos + ll)))
+        pos += ll + ml
+    return seqs
+
+
+def _shuffled(codes_, seed):
+    """a fixed shuffle whose first code is not 0"""
+    out = list(codes_)
+    random.Random(seed).shuffle(out)
+    k = next(i for i, c in enumerate(out) if c)
+    return out[k:] + out[:k]
+
+
+def _without(top, absent):
+    return [c for c in range(top + 1) if c not in absent]
+
+
+def family_n():
+    """the two ways out of the table normalisation that no parse of text reaches (branch_cases.tans_histograms; ze_tans_shares_rare's `settled == n` and `left == 0`):
+    22, 43 and 44 sequences with every code of a table exactly once, without and with absent codes below the largest.  At level 5 (lazy to 16 KiB) every
+    table is normalised for the cost estimate (ZSTD_NCountCost) whichever mode wins; below lazy so few sequences take the predefined tables unseen, and
+    the frames are the plain regression they are for every family.  The offset alphabet cannot take part: 22 different offset codes need an offset of 2 MiB, and the
+    records hold offBase in 24 bits beside its code, so no code above 23 exists here (the entries refuse offsets beyond the window before the stage sees them).
+    The conditions are asserted in tests/test_emu_seqrecords.py."""
+    out = []
+
+    def n_case(name, ll, ml, seed):
+        out.append(case("N", name, _code_values(_shuffled(ll, seed), _shuffled(ml, seed + 1)), tail=300, ext_rep=bool(seed % 2)))
+    n_case("22/settled", range(22), range(22), 1)                                        # LL 22 of 22, ML 22 of 22 at table log 5
+    n_case("22/gaps", _without(31, (0, 3, 4, 9, 13, 14, 20, 25, 26, 30)), _without(47, (1, 2, 5, 6, 7, 10, 11, 12, 15, 16, 17, 18, 19, 21, 22, 23, 28, 29, 33, 34, 35, 40, 41, 42, 45, 46)), 4)
+    ll_many = [i % 20 for i in range(44)]                                                # (36 literal-length codes: 43 cannot all differ)
+    n_case("43/settled", ll_many[:43], range(43), 7)                                     # ML 43 of 43 at table log 6
+    n_case("44/settled", ll_many, range(44), 10)
+    n_case("44/gaps", ll_many, _without(47, (0, 9, 20, 41)), 13)                         # ML 44 of 48
+    n_case("43/gaps", ll_many[:43], _without(45, (3, 17, 33)), 16)                       # ML 43 of 46
+    return out
+
+
 # ------------------------------------------------------------------------------------------------------------------------
 # frames of several caller-cut blocks: the state the entropy stage carries from block to block (the previous Huffman table, the previous tANS tables, and — through
 # the records — the repcodes, which only a compressed block confirms)
@@ -560,7 +604,7 @@ def mfamily(name):
     return _mcases[name]
 
 
-FAMILIES = {"G": family_g, "L": family_l, "S": family_s, "M": family_m, "W": family_w, "R": family_r, "B": family_b, "U": family_u}
+FAMILIES = {"G": family_g, "L": family_l, "S": family_s, "M": family_m, "W": family_w, "R": family_r, "B": family_b, "U": family_u, "N": family_n}
 _cases = {}
 
 

@@ -302,6 +302,59 @@ def tight():
     return _memo("tight", build)
 
 
+SKIPPED = "skipped/"                            # a case's name begins so: the conversion kernel writes the slot's word itself and converts nothing
+
+
+def mixed_level5():
+    """two lists for ONE call each at level 5: 36 served frames of 1-4 KiB and, between them, the same source just over 128 KiB — the level has no row for it, the
+    conversion skips the frame (block count 0) and the frame loop answers 201.  The skipped frame sits at indices 0, middle and last of the first list, at 1 and
+    the middle of the second; the caller runs both orders, so that a workgroup meets a skipped frame and then served ones (zj_seq_convert_kernel's one lane-0 store)."""
+    def build():
+        big = prose(131073 + 2000, seed=43)
+        skipped = Case(SKIPPED + "level5/133073", big, generated(big, 5), 5, REPCODES, True)
+        served = []
+        for i in range(36):
+            data = prose(1024 + 83 * i, seed=4300 + i)
+            served.append(Case(f"mixed5/{i}", data, generated(data, 5), 5, REPCODES, True))
+        a = [skipped] + served[:18] + [skipped] + served[18:] + [skipped]
+        b = served[:1] + [skipped] + served[1:20] + [skipped] + served[20:]
+        return [a, b]
+    return _memo("mixed5", build)
+
+
+def mixed_descending(at, n=40):
+    """n frames of 1-4 KiB at level 3 for ONE call in which frame `at`'s pair of sequence offsets descends by one row (run_descending below lays the rows out): the
+    frame loop answers 107 for that slot alone (zs_compress_frame: ZS_NO_FRAME -> externalSequences_invalid).  The frame in front of it then owns one row more — the
+    first row of the frame behind, which lies behind its closing delimiter and is never looked at; its case says so, so the reference is asked the same."""
+    def build():
+        out = []
+        for i in range(n):
+            data = prose(1024 + 71 * i, seed=4700 + i)
+            out.append(Case(f"descend{at}/{i}", data, generated(data, 3), 3, 0, True))
+        out[at] = out[at]._replace(name=SKIPPED + f"descend{at}/{at}", decodes=False)
+        if at > 0:
+            out[at - 1] = out[at - 1]._replace(seqs=out[at - 1].seqs + [out[at + 1].seqs[0]])
+        return out
+    return _memo(("descending", at, n), build)
+
+
+def descending_rows(cases, at):
+    """(rows, seq_off) of a call for mixed_descending(at): frame `at` has no rows of its own and the pair (seq_off[at], seq_off[at + 1]) = (B + 1, B), B the first
+    row of frame at + 1; every other pair ascends"""
+    rows, seq_off = [], []
+    for i, c in enumerate(cases):
+        if i == at:
+            seq_off.append(len(rows) + 1)
+            continue
+        seq_off.append(len(rows))
+        rows += c.seqs[:-1] if i == at - 1 else c.seqs
+    seq_off.append(len(rows))
+    if at > 0:
+        assert cases[at - 1].seqs[-1] == cases[at + 1].seqs[0] and seq_off[at - 1] + len(cases[at - 1].seqs) == seq_off[at]
+    assert [i for i in range(len(cases)) if seq_off[i] > seq_off[i + 1]] == [at] and seq_off[at] - seq_off[at + 1] == 1
+    return rows, seq_off
+
+
 def every_case():
     return smallest() + from_generator() + multi_block() + long_codes()
 

@@ -78,6 +78,8 @@ def test_refuses_more_records_than_a_slot_holds(emu):
     rec = (C.c_uint * 4)(1, 3, 1, 0)
     dst = C.create_string_buffer(1024)
     assert emu.emu_compress_records(b"a" * 100, 100, rec, 65536 // 4 + 17, 1, 0, dst, 1024, 3) >= 1 << 63
+    wide = (C.c_uint * 4)(4, 4, 1 << 24, 0)                          # an offBase that does not fit beside its code in the record
+    assert emu.emu_compress_records(b"abcdefgh" * 8, 64, wide, 1, 60, 56, dst, 1024, 3) >= 1 << 63
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -317,3 +319,26 @@ def test_bound_of_the_pipelined_parse(oracle_ref):
         assert b.shape["blocks"][0]["modes"] == [2, 2, 2], cname
         ll, of, ml = (set(x) for x in R.codes(b.rec))
         assert ll >= set(range(16)) | {16, 18, 20, 22, 24, 25, 26, 27, 28} and ml >= set(range(33)) and of >= set(range(2, 17)), (cname, sorted(ll), sorted(of), sorted(ml))
+
+
+def test_family_n_takes_the_rare_ways_out(oracle_ref):
+    """every frame of family N (level 5, lazy, estimates every table's cost): the reference's model of the normalisation
+    (branch_cases.normalise_exit, at the table log FSE_optimalTableLog picks, on the histogram ZSTD_buildCTable would count) takes the way out the case is
+    named for — every symbol settled and nothing open, each in the literal-length and the match-length alphabet, at table logs 5 and 6"""
+    from branch_cases import normalise_exit
+    lib = oracle_ref.lib()
+    lib.FSE_optimalTableLog.restype = C.c_uint
+    lib.FSE_optimalTableLog.argtypes = [C.c_uint, C.c_size_t, C.c_uint]
+    seen = set()
+    for c, level, b in blocks_of("N"):
+        k = b.shape["blocks"][0]
+        assert k["type"] == 2 and len(b.content) < 16384 and set(R.levels_of(c)) == {1, 3, 4, 5}, (c.name, level, k)
+        ways = []
+        for t, codes in enumerate(R.codes(b.rec)):
+            hist = [codes.count(s) for s in range(max(codes) + 1)]
+            log = lib.FSE_optimalTableLog((9, 8, 9)[t], len(codes), max(codes))          # LLFSELog, OffFSELog, MLFSELog
+            ways.append(normalise_exit(hist, len(codes), log, False)[0])
+            seen.add((R.M_NAMES[t], ways[-1], log))
+        want = "settled-all" if c.name.endswith("/settled") else "nothing-open"
+        assert ways[2] == want and (ways[0] == want or b.nb > 22), (c.name, ways)
+    assert {("LL", "settled-all", 5), ("LL", "nothing-open", 5), ("ML", "settled-all", 5), ("ML", "nothing-open", 5), ("ML", "settled-all", 6), ("ML", "nothing-open", 6)} <= seen, seen

@@ -103,6 +103,30 @@ def test_emu_sequences_batch_frames_and_refusals(emu, oracle_ref):
     assert refused == sum(not c.decodes for c in cases) == 18                # every tenth frame, but the two whose damage lies behind the last block
 
 
+def test_emu_sequences_mixed_skipped_and_served(emu, oracle_ref):
+    """the answers of the lists tests/test_gpu_sequences.py puts into one call each: served frames are the reference's, a source just over 128 KiB at level 5 has no
+    row here (201) though the reference writes a frame, and a slot without a slice of the array (its offsets descend) is externalSequences_invalid"""
+    for cases in SC.mixed_level5():
+        skipped = [c for c in cases if c.name.startswith(SC.SKIPPED)]
+        assert 2 <= len(skipped) <= 3 and len(cases) - len(skipped) == 36
+        assert run(emu, skipped[0]) == -201 and isinstance(SC.expected(skipped[0]), bytes) and len(skipped[0].data) > 131072
+        for c in cases:
+            if not c.name.startswith(SC.SKIPPED):
+                SC.check(c, run(emu, c), oracle_ref)
+    emu.emu_compress_no_frame.restype = C.c_ulonglong
+    emu.emu_compress_no_frame.argtypes = [C.c_char_p, C.c_uint, C.c_void_p, C.c_uint, C.c_int, C.c_uint]
+    for at in (0, 1, 20):
+        cases = SC.mixed_descending(at)
+        rows, seq_off = SC.descending_rows(cases, at)
+        for i, c in enumerate(cases):
+            if i == at:
+                dst = C.create_string_buffer(256)
+                assert emu.emu_compress_no_frame(c.data, len(c.data), dst, 256, c.level, c.flags) == (1 << 64) - SC.E_SEQUENCES
+            else:
+                assert rows[seq_off[i]:seq_off[i + 1]] == c.seqs               # the slice the call gives the frame is the array the reference is asked about
+                SC.check(c, run(emu, c), oracle_ref)
+
+
 def test_emu_sequences_every_capacity(emu, oracle_ref):
     for c in SC.tight():
         full = SC.expected(c)

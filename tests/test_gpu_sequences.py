@@ -29,8 +29,9 @@ def roomy(c):
     return len(c.data) + (len(c.data) >> 8) + 128 + 3 * (len(c.seqs) + 1)
 
 
-def run_batch(gpu, cases, caps=None, grid=0):
-    """one call for `cases` (same level and flags): [bytes or -code].  caps: a destination capacity per case (default: roomy)."""
+def run_batch(gpu, cases, caps=None, grid=0, layout=None):
+    """one call for `cases` (same level and flags): [bytes or -code].  caps: a destination capacity per case (default: roomy).  layout: (rows, seq_off) where the
+    sequence array is not simply the cases' arrays one behind the other"""
     import torch
     level, flags = cases[0].level, cases[0].flags
     assert all(c.level == level and c.flags == flags for c in cases)
@@ -41,10 +42,14 @@ def run_batch(gpu, cases, caps=None, grid=0):
     for c, cap in zip(cases, caps):
         src_off.append(src_off[-1] + len(c.data)); seq_off.append(seq_off[-1] + len(c.seqs)); dst_off.append(dst_off[-1] + cap)
     dev = "cuda"
-    rows = seq_off[-1]
+    all_rows = [s for c in cases for s in c.seqs]
+    if layout is not None:
+        all_rows, seq_off = layout
+        assert len(seq_off) == n + 1 and max(seq_off) <= len(all_rows) + 1
+    rows = len(all_rows)
     seq_h = np.full((rows + 2 * GUARD, 4), 0xA7A7A7A7, dtype=np.uint32)                  # guard rows on both sides of the array
     if rows:
-        seq_h[GUARD:GUARD + rows] = np.array([v for c in cases for v in SC.flat(c.seqs)], dtype=np.uint32).reshape(-1, 4)
+        seq_h[GUARD:GUARD + rows] = np.array(SC.flat(all_rows), dtype=np.uint32).reshape(-1, 4)
     seq_d = torch.from_numpy(seq_h.view(np.int32)).to(dev)
     src = torch.frombuffer(bytearray(b"".join(c.data for c in cases) or b"\0"), dtype=torch.uint8).to(dev)
     dst_h = np.full(dst_off[-1] + GUARD, 0x5C, dtype=np.uint8)
@@ -153,3 +158,33 @@ def test_gpu_sequences_host_forms_and_bound(gpu, oracle_ref):
         got = -((1 << 64) - res[i]) if res[i] >= 1 << 63 else dsts[i].raw[:res[i]]
         SC.check(c, got, oracle_ref)
     assert L.zjni_isError(L.zjni_compress_sequences_batch(None, None, None, None, None, None, res, 1, 3, 0)) and L.zjni_isError(L.zjni_compress_sequences(None, 0, None, 0, None, 0, 3, 16))
+
+
+def check_mixed(gpu, oracle_ref, cases, code, grid, layout=None):
+    """every served slot the reference's frame, every skipped slot its code (run_batch has looked at the guards)"""
+    got = run_batch(gpu, cases, grid=grid, layout=layout)
+    assert len(got) == len(cases)
+    for c, g in zip(cases, got):
+        if c.name.startswith(SC.SKIPPED):
+            assert g == -code, (c.name, grid, g if isinstance(g, int) else len(g))
+        else:
+            SC.check(c, g, oracle_ref)
+
+
+@pytest.mark.parametrize("grid", (1, 2, 0))
+def test_gpu_sequences_level5_skipped_frames_among_served(gpu, oracle_ref, grid):
+    """one call at level 5 in which frames the entry does not serve (just over 128 KiB: 201, the conversion writes block count 0 and moves on) stand at index 0, 1, in
+    the middle and last among 36 served ones, in both orders, through one workgroup, two, and the default grid"""
+    for cases in SC.mixed_level5():
+        assert 2 <= sum(c.name.startswith(SC.SKIPPED) for c in cases) <= 3 and len(cases) >= 38
+        for order in (cases, cases[::-1]):
+            check_mixed(gpu, oracle_ref, order, 201, grid)
+
+
+@pytest.mark.parametrize("grid", (1, 2, 0))
+@pytest.mark.parametrize("at", (0, 1, 20))
+def test_gpu_sequences_one_descending_pair_among_served(gpu, oracle_ref, at, grid):
+    """one call at level 3 in which ONE frame's pair of sequence offsets descends: the conversion marks the slot ZS_NO_FRAME, for which the frame loop answers
+    externalSequences_invalid (zs_compress_frame), and every other frame of the call is the reference's"""
+    cases = SC.mixed_descending(at)
+    check_mixed(gpu, oracle_ref, cases, SC.E_SEQUENCES, grid, layout=SC.descending_rows(cases, at))

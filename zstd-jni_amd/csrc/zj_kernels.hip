@@ -3798,12 +3798,19 @@ __global__ __launch_bounds__(64) void zj_seq_convert_kernel(const u64* __restric
         u32 const i = zj_next_index(workCounter);
         if (i >= n) break;
         u64 const q0 = zj_uni64(seqOff[i]), q1 = zj_uni64(seqOff[i + 1]), s0 = zj_uni64(srcOff[i]), s1 = zj_uni64(srcOff[i + 1]);
-        if (q0 > q1 || q1 > total || q1 - q0 > 0x7FFFFFFFull || s1 < s0) { if (threadIdx.x == 0) nBlk[i] = ZS_NO_FRAME; continue; }
-        u64 const size64 = s1 - s0;
-        u32 const srcSize = size64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)size64;
-        ZEParams const p = ze_params_of(level, srcSize);
-        if (p.strategy == 0u || srcSize > ZE_MULTI_MAX) { if (threadIdx.x == 0) nBlk[i] = 0u; continue; }       // the frame loop answers 201 before it looks at a slot
-        zs_convert(g, seqs + q0, (u32)(q1 - q0), srcSize, zs_ml_min(p), zs_max_nbseq(p, srcSize), (flags & ZS_FLAG_REPCODES) != 0u, rec + q0 + i, lit + q0 + i, nBlk + i);
+        // The shape of zj_seq_cut_kernel, for its reason: one way through the body and ONE place where lane 0 alone writes, with the workgroup's barrier
+        // between it and the next index (a lane-0 store that `continue`s into zj_next_index lets the compiler send the other 63 lanes ahead on their own).
+        u32 answer = 1u;                                                                                         // 1: convert; else the word for nBlk[i]
+        if (q0 > q1 || q1 > total || q1 - q0 > 0x7FFFFFFFull || s1 < s0) answer = ZS_NO_FRAME;
+        else {
+            u64 const size64 = s1 - s0;
+            u32 const srcSize = size64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (u32)size64;
+            ZEParams const p = ze_params_of(level, srcSize);
+            if (p.strategy == 0u || srcSize > ZE_MULTI_MAX) answer = 0u;                                         // the frame loop answers 201 before it looks at a slot
+            else zs_convert(g, seqs + q0, (u32)(q1 - q0), srcSize, zs_ml_min(p), zs_max_nbseq(p, srcSize), (flags & ZS_FLAG_REPCODES) != 0u, rec + q0 + i, lit + q0 + i, nBlk + i);
+        }
+        if (answer != 1u && threadIdx.x == 0) nBlk[i] = answer;
+        __syncthreads();
     }
 }
 // (the register budget of zj_encode_kernel, whose stage this is: three waves per SIMD)
