@@ -8,6 +8,7 @@ LINES = {
     "tans-settled-all": ("zj_encode.h", "share[s] = (short)(share[s] + (i32)cells); }"),
     "tans-nothing-open": ("zj_encode.h", "(rank < cells % holders ? 1 : 0)"),
     "wave-count-back-second-trip": ("zj_match_wavex.h", "if (total + 512u >= limit) return ZJ_UNI(limit);"),
+    "lds-wave-count-back-second-trip": ("zj_match_wave.h", "if (total + 512u >= limit) return limit;"),
     "lane-back-goes-on": ("zj_match_lane.h", "vb = true; bp0 = ip - bk; bp1 = mpos - bk;"),
     "gated-lane-back-goes-on": ("zj_match_lane.h", "vb = true; bp0 = ip0 - bk; bp1 = mpos - bk;"),
     "run-back-goes-on": ("zj_match_run.h", "bk += e; more = (e == 8u) && (limit > 8u);"),
@@ -18,7 +19,10 @@ LINES = {
     "top64": ("zj_decode_split.h", "return s == 64u ? lo : (lo << (s - 64u));"),
 }
 # the tests that run the cases (tests/test_emu_reached.py counts the lines over exactly these)
-CASE_TESTS = ("tests/test_emu_branches.py", "tests/test_emu_tans.py::test_the_rare_ways_out_equal_the_references", "tests/test_emu_seqrecords.py::test_family_is_the_references_frame[N]")
+CASE_TESTS = ("tests/test_emu_branches.py", "tests/test_emu_tans.py::test_the_rare_ways_out_equal_the_references", "tests/test_emu_seqrecords.py::test_family_is_the_references_frame[N]",
+              "tests/test_emu_wave.py::test_wave_matcher_long_backward_extensions")
+# the emulation libraries that hold the lines (tools/emu_coverage.py counts these; the others load from the tree as usual)
+CASE_LIBS = ("emu", "emu_wave")
 
 # ---- ze_tans_shares_rare: the ways out of FSE_normalizeCount ----
 _RTB = [0, 473195, 504333, 520860, 550000, 700000, 750000, 830000]
@@ -150,6 +154,50 @@ def backward_inputs():
     """[(name, data)]"""
     return [("late/24000", late_copy(24000, 4000, more=100)), ("late/16000", late_copy(16000, 4000, more=100)), ("doubled/20000", doubled(20000)), ("doubled/3000", doubled(3000)),
             ("spliced/20000", spliced(20000, 15000)), ("across-blocks", across_blocks()), ("second-block/deep", deep_in_second_block())]
+
+
+# ---- the same for the wave matcher with its tables in LDS (zj_match_wave.h: level 3 with hashLog 14 / chainLog 13, frames to 64 KiB) ----
+# Its backward count takes the first 128 bytes in the round that also counts forwards (extend) and the rest in count_back, 512 bytes a trip.  The parse of
+# late_copy(24 000, 4 000) finds the copy LDS_WAVE_FOUND bytes into the frame, 1 843 bytes into the copy — measured once on the lane-serial build and asserted since:
+# the reference's first sequence of that frame has 24 000 literals (the match begins at the copy's first byte).  One changed byte in the copy, `back` + 1 bytes in
+# front of that position, ends the extension there instead: the position where the copy is found does not move (the parse has not found anything yet and strides
+# over the changed byte as over the others), so the extension is exactly `back` bytes and the first sequence has LDS_WAVE_FOUND - back literals.
+LDS_WAVE_N, LDS_WAVE_LATE, LDS_WAVE_FOUND = 24000, 4000, 25843
+# back - 128 is what count_back counts: 384 (a mismatch inside the first trip), 511 / 512 / 513 (the first trip runs through: the line after it asks whether the
+# limit is reached, and the second trip ends in its first lane, its first byte or its second), 1 023 / 1 024 / 1 025 (the same around the third trip), 1 715 (the
+# copy's first byte, four trips)
+LDS_WAVE_BACKS = (512, 639, 640, 641, 1151, 1152, 1153, 1843)
+
+
+def lds_wave_backward_inputs():
+    """[(name, data, back)]: backward extensions of exactly `back` bytes on the LDS wave matcher"""
+    base = late_copy(LDS_WAVE_N, LDS_WAVE_LATE, more=100)
+    out = []
+    for back in LDS_WAVE_BACKS:
+        d = bytearray(base)
+        if back < LDS_WAVE_FOUND - LDS_WAVE_N:
+            d[LDS_WAVE_FOUND - back - 1] ^= 0xFF
+        out.append((f"lds-wave/back-{back}", bytes(d), back))
+    return out
+
+
+def lds_wave_first_sequence(data):
+    """(offset, litLength, matchLength) of the first sequence of the reference's own parse at level 3 with hashLog 14 / chainLog 13 (ZSTD_generateSequences)"""
+    import ctypes as C
+    import sequences_cases as SC
+    from oracle import ref
+    L = SC._lib()
+    cctx = L.ZSTD_createCCtx()
+    try:
+        for p, v in ((100, 3), (102, 14), (103, 13), (1008, 1)):               # ZSTD_c_compressionLevel, ZSTD_c_hashLog, ZSTD_c_chainLog, explicit block delimiters
+            ref._check(L.ZSTD_CCtx_setParameter(cctx, p, v))
+        cap = L.ZSTD_sequenceBound(len(data))
+        arr = (SC._Seq * cap)()
+        n = ref._check(L.ZSTD_generateSequences(cctx, arr, cap, bytes(data), len(data)))
+        assert n >= 1
+        return arr[0].offset, arr[0].litLength, arr[0].matchLength
+    finally:
+        L.ZSTD_freeCCtx(cctx)
 
 
 # ---- decoder lines ----

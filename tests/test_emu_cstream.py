@@ -6,9 +6,10 @@ the state's counters show that no byte was parsed twice.  The -m gpu twin is tes
 import ctypes as C
 import os
 import random
-import subprocess
 
 import pytest
+
+from util import emu_so
 
 from conftest import golden
 
@@ -23,9 +24,7 @@ def window(level):
 
 @pytest.fixture(scope="module")
 def emu():
-    d = os.path.join(ROOT, "tests", "emu_cstream")
-    subprocess.check_call(["make", "-s", "-C", d])
-    L = C.CDLL(os.path.join(d, "libzjni_emu_cstream.so"))
+    L = C.CDLL(emu_so("emu_cstream", "libzjni_emu_cstream.so"))
     L.emu_cs_state_bytes.restype = C.c_uint
     L.emu_cs_state_bytes.argtypes = [C.c_int]
     sig = [C.c_char_p, C.c_uint, C.c_char_p, C.c_uint, C.c_int, C.c_int, C.POINTER(C.c_uint), C.c_uint, C.c_int, C.c_int]

@@ -7,9 +7,10 @@ byte for byte.  The -m gpu twin is tests/test_gpu_cstream_pieces.py."""
 import ctypes as C
 import os
 import random
-import subprocess
 
 import pytest
+
+from util import emu_so
 
 from conftest import golden
 
@@ -26,9 +27,7 @@ def window(level):
 
 @pytest.fixture(scope="module")
 def emu():
-    d = os.path.join(ROOT, "tests", "emu_cstream_pieces")
-    subprocess.check_call(["make", "-s", "-C", d])
-    L = C.CDLL(os.path.join(d, "libzjni_emu_cstream_pieces.so"))
+    L = C.CDLL(emu_so("emu_cstream_pieces", "libzjni_emu_cstream_pieces.so"))
     L.emu_csp_state_bytes.restype = C.c_uint
     L.emu_csp_state_bytes.argtypes = [C.c_int]
     L.emu_csp_continue.restype = C.c_ulonglong

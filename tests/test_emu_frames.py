@@ -10,10 +10,11 @@ zjni_compressBound_chunked.  The -m gpu twin is tests/test_gpu_frames.py."""
 import ctypes as C
 import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
+
+from util import emu_so
 
 import inspect_cases as ic
 
@@ -24,9 +25,7 @@ U64P = C.POINTER(C.c_ulonglong)
 
 @pytest.fixture(scope="module")
 def emu():
-    d = os.path.join(ROOT, "tests", "emu_frames")
-    subprocess.check_call(["make", "-s", "-C", d])
-    L = C.CDLL(os.path.join(d, "libzjni_emu_frames.so"))
+    L = C.CDLL(emu_so("emu_frames", "libzjni_emu_frames.so"))
     L.emu_frames_count.restype = C.c_ulonglong
     L.emu_frames_count.argtypes = [C.c_void_p, C.c_void_p, C.c_uint, C.c_void_p]
     L.emu_frames_emit.restype = None

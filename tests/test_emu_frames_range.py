@@ -9,10 +9,11 @@ residue pair.  The -m gpu twin is tests/test_gpu_frames_range.py."""
 import ctypes as C
 import itertools
 import os
-import subprocess
 
 import numpy as np
 import pytest
+
+from util import emu_so
 
 import inspect_cases as ic
 from test_emu_frames import crafted
@@ -32,9 +33,7 @@ class Rec(C.Structure):
 
 @pytest.fixture(scope="module")
 def emu():
-    d = os.path.join(ROOT, "tests", "emu_frames_range")
-    subprocess.check_call(["make", "-s", "-C", d])
-    L = C.CDLL(os.path.join(d, "libzjni_emu_frames_range.so"))
+    L = C.CDLL(emu_so("emu_frames_range", "libzjni_emu_frames_range.so"))
     vp = C.c_void_p
     L.emu_range_count.restype = None
     L.emu_range_count.argtypes = [vp, vp, vp, vp, C.c_uint, vp, vp, vp]

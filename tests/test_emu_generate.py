@@ -5,9 +5,10 @@ scratch, tables) is poisoned once and outlives every frame, as a persistent work
 canaries the emulation checks itself.  The -m gpu twin is tests/test_gpu_generate.py."""
 import ctypes as C
 import os
-import subprocess
 
 import pytest
+
+from util import emu_so
 
 import generate_cases as GC
 import sequences_cases as SC
@@ -18,9 +19,7 @@ TOUCHED = 0xFFFFFFFFFFFF0001
 
 @pytest.fixture(scope="module")
 def emu():
-    d = os.path.join(ROOT, "tests", "emu_generate")
-    subprocess.check_call(["make", "-s", "-C", d])
-    L = C.CDLL(os.path.join(d, "libzjni_emu_generate.so"))
+    L = C.CDLL(emu_so("emu_generate", "libzjni_emu_generate.so"))
     L.emu_generate.restype = C.c_ulonglong
     L.emu_generate.argtypes = [C.c_char_p, C.c_uint, C.c_int, C.c_void_p, C.c_ulonglong, C.c_int]
     L.emu_export_records.restype = C.c_ulonglong
@@ -34,9 +33,7 @@ def emu():
 
 @pytest.fixture(scope="module")
 def emu_seq():
-    d = os.path.join(ROOT, "tests", "emu_sequences")
-    subprocess.check_call(["make", "-s", "-C", d])
-    L = C.CDLL(os.path.join(d, "libzjni_emu_sequences.so"))
+    L = C.CDLL(emu_so("emu_sequences", "libzjni_emu_sequences.so"))
     L.emu_compress_sequences.restype = C.c_ulonglong
     L.emu_compress_sequences.argtypes = [C.c_char_p, C.c_uint, C.c_void_p, C.c_uint, C.c_void_p, C.c_uint, C.c_int, C.c_uint]
     return L

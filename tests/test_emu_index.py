@@ -12,12 +12,12 @@ import ctypes as C
 import itertools
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
 import pieces_cases as pc
+from util import emu_so
 import test_emu_frames_range as fr
 from test_emu_frames_range import Rec, arr, ptr, MAXU, ERROR, FILL
 
@@ -32,9 +32,7 @@ class Req(C.Structure):
 
 
 def _load(directory, name):
-    d = os.path.join(ROOT, "tests", directory)
-    subprocess.check_call(["make", "-s", "-C", d])
-    return C.CDLL(os.path.join(d, name))
+    return C.CDLL(emu_so(directory, name))
 
 
 @pytest.fixture(scope="module")

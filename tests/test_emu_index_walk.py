@@ -17,6 +17,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from util import emu_so
 import test_emu_frames_range as fr
 import test_emu_index as ti
 from test_emu_index import emu as index_emu, range_emu, true_index      # noqa: F401  (the two fixtures by their names)
@@ -32,8 +33,7 @@ HERE = os.path.join(ROOT, "tests", "emu_index_walk")
 
 @pytest.fixture(scope="module")
 def walk():
-    subprocess.check_call(["make", "-s", "-C", HERE])
-    L = C.CDLL(os.path.join(HERE, "libzjni_emu_index_walk.so"))
+    L = C.CDLL(emu_so("emu_index_walk", "libzjni_emu_index_walk.so"))
     vp, ull = C.c_void_p, C.c_ulonglong
     L.emu_walk_count.restype = None
     L.emu_walk_count.argtypes = [vp, vp, ull, vp]

@@ -10,7 +10,7 @@ from conftest import golden
 import ctypes as C
 import os
 
-from util import ROOT, emu_lib, emu_compress_multi, emu_decompress
+from util import ROOT, emu_lib, emu_so, emu_compress_multi, emu_decompress
 
 
 @pytest.fixture(scope="module")
@@ -117,7 +117,7 @@ def test_multiblock_wave_matcher_orders_and_switches(emu, oracle_ref, zj):
     ZE_FLAG_MULTI_SERIAL: every variant gives the reference's frame.  Inputs: what drives windows wider than a hit (noise, long
     literal runs), equal hashes inside a window (two-letter alphabets, byte runs), matches longer than the staged span, matches that
     reach back over block borders, steps above 1."""
-    rev = C.CDLL(os.path.join(ROOT, "tests", "emu", "libzjni_emu_rev.so"))
+    rev = C.CDLL(emu_so("emu", "libzjni_emu_rev.so"))
     rev.emu_compress_multi.restype = C.c_ulonglong
     rev.emu_compress_multi.argtypes = [C.c_char_p, C.c_uint, C.c_char_p, C.c_uint, C.c_uint]
     rnd = random.Random(12)
@@ -146,7 +146,7 @@ def test_level3_single_block_frames_on_the_wave_route(emu, oracle_ref, zj):
     one block over HBM tables with the level's own table sizes (16 / 15: the reference's plain level 3) or the caller's; frames below 64 bytes take
     the one-lane parse there"""
     from util import edge_inputs
-    rev = C.CDLL(os.path.join(ROOT, "tests", "emu", "libzjni_emu_rev.so"))
+    rev = C.CDLL(emu_so("emu", "libzjni_emu_rev.so"))
     rev.emu_compress_multi.restype = C.c_ulonglong
     rev.emu_compress_multi.argtypes = [C.c_char_p, C.c_uint, C.c_char_p, C.c_uint, C.c_uint]
     rnd = random.Random(21)

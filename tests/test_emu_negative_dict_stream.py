@@ -7,12 +7,11 @@ without a pledged size (oracle/ref.py compress_stream) up to the 512 KiB window.
 import ctypes as C
 import os
 import random
-import subprocess
 
 import pytest
 
 from conftest import golden
-from util import json_records
+from util import json_records, emu_so
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LEVELS = [-1, -2, -3, -7, -50, -1000, -131072, -200000]
@@ -22,9 +21,7 @@ SOURCE_SIZES = [0, 1, 7, 8, 100, 8191, 8192, 8193, 16384, 65536, 131071, 131072]
 
 @pytest.fixture(scope="module")
 def emu():
-    d = os.path.join(ROOT, "tests", "emu_negdict")
-    subprocess.check_call(["make", "-s", "-C", d])
-    L = C.CDLL(os.path.join(d, "libzjni_emu_negdict.so"))
+    L = C.CDLL(emu_so("emu_negdict", "libzjni_emu_negdict.so"))
     L.emu_nd_level_word.restype = C.c_uint
     L.emu_nd_level_word.argtypes = [C.c_int]
     L.emu_nd_cdict_create.restype = C.c_void_p

@@ -7,12 +7,11 @@ tests/test_gpu_negative_levels.py."""
 import ctypes as C
 import os
 import random
-import subprocess
 
 import pytest
 
 from conftest import golden
-from util import edge_inputs
+from util import edge_inputs, emu_so
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LEVELS = [-1, -2, -3, -4, -5, -7, -17, -100, -65536, -131072, -200000]
@@ -21,9 +20,7 @@ ZE_FLAG_CHECKSUM, ZE_FLAG_NO_FCS = 1, 2
 
 @pytest.fixture(scope="module")
 def emu():
-    d = os.path.join(ROOT, "tests", "emu_fast")
-    subprocess.check_call(["make", "-s", "-C", d])
-    L = C.CDLL(os.path.join(d, "libzjni_emu_fast.so"))
+    L = C.CDLL(emu_so("emu_fast", "libzjni_emu_fast.so"))
     L.emu_fast_compress.restype = C.c_ulonglong
     L.emu_fast_compress.argtypes = [C.c_char_p, C.c_uint, C.c_char_p, C.c_uint, C.c_int, C.c_uint, C.c_int]
     L.emu_fast_params.argtypes = [C.c_int, C.c_uint, C.POINTER(C.c_uint)]

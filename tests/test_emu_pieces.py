@@ -9,12 +9,12 @@ zjni_compressBound.  The -m gpu twin is tests/test_gpu_pieces.py."""
 import ctypes as C
 import os
 import random
-import subprocess
 
 import numpy as np
 import pytest
 
 from pieces_cases import bound, illegal, lay_out, legal
+from util import emu_so
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MAXU = (1 << 64) - 1
@@ -23,9 +23,7 @@ CHUNK = 1000
 
 
 def _load(name, sub):
-    d = os.path.join(ROOT, "tests", sub)
-    subprocess.check_call(["make", "-s", "-C", d])
-    return C.CDLL(os.path.join(d, name))
+    return C.CDLL(emu_so(sub, name))
 
 
 @pytest.fixture(scope="module")

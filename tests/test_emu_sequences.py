@@ -5,9 +5,10 @@ decodes to the source.  The emulation's workgroup state (uniforms, LDS, scratch)
 sequence array, slots and destination are exact-size heap blocks.  The -m gpu twin is tests/test_gpu_sequences.py."""
 import ctypes as C
 import os
-import subprocess
 
 import pytest
+
+from util import emu_so
 
 import sequences_cases as SC
 
@@ -16,9 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def emu():
-    d = os.path.join(ROOT, "tests", "emu_sequences")
-    subprocess.check_call(["make", "-s", "-C", d])
-    L = C.CDLL(os.path.join(d, "libzjni_emu_sequences.so"))
+    L = C.CDLL(emu_so("emu_sequences", "libzjni_emu_sequences.so"))
     L.emu_compress_sequences.restype = C.c_ulonglong
     L.emu_compress_sequences.argtypes = [C.c_char_p, C.c_uint, C.c_void_p, C.c_uint, C.c_void_p, C.c_uint, C.c_int, C.c_uint]
     L.emu_sequence_bound.restype = C.c_ulonglong

@@ -5,9 +5,10 @@ frame, that frame decodes to the source.  The emulation's workgroup state is poi
 and destination are exact-size heap blocks.  The -m gpu twin is tests/test_gpu_sequences_nodelim.py."""
 import ctypes as C
 import os
-import subprocess
 
 import pytest
+
+from util import emu_so
 
 import sequences_nodelim_cases as NC
 
@@ -16,9 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def emu():
-    d = os.path.join(ROOT, "tests", "emu_sequences_nodelim")
-    subprocess.check_call(["make", "-s", "-C", d])
-    L = C.CDLL(os.path.join(d, "libzjni_emu_sequences_nodelim.so"))
+    L = C.CDLL(emu_so("emu_sequences_nodelim", "libzjni_emu_sequences_nodelim.so"))
     L.emu_compress_sequences_nodelim.restype = C.c_ulonglong
     L.emu_compress_sequences_nodelim.argtypes = [C.c_char_p, C.c_uint, C.c_void_p, C.c_uint, C.c_void_p, C.c_uint, C.c_int, C.c_uint, C.POINTER(C.c_uint)]
     L.emu_nodelim_max_blocks.restype = C.c_uint

@@ -8,6 +8,7 @@ import random
 import pytest
 
 from conftest import golden
+import branch_cases as B
 from util import edge_inputs, emu_wave_libs, emu_compress_wave, equal_count_inputs
 
 
@@ -75,3 +76,14 @@ def test_wave_matcher_equal_counts(waves, oracle_ref):
     for name, d in equal_count_inputs():
         if 64 <= len(d) <= 65536:
             check(waves, oracle_ref, d, name)
+
+
+def test_wave_matcher_long_backward_extensions(waves, oracle_ref):
+    """branch_cases.lds_wave_backward_inputs: a copy of noise found 1 843 bytes in and extended backwards over exactly 512 .. 1 843 bytes — count_back beyond its first
+    trip of 512 bytes, which no other input of this file reaches (tests/test_emu_reached.py keeps the line reached).  The reference's own parse says that the extension
+    has the length the case is named for; both lane orders give its frame."""
+    for name, data, back in B.lds_wave_backward_inputs():
+        off, ll, ml = B.lds_wave_first_sequence(data)
+        assert (off, ll) == (B.LDS_WAVE_N - B.LDS_WAVE_LATE, B.LDS_WAVE_FOUND - back), (name, off, ll, ml)
+        assert ml >= back + 8, (name, ml)
+        check(waves, oracle_ref, data, name)

@@ -33,6 +33,18 @@ def test_gpu_backward_extensions_on_the_wave_matcher(gpu, oracle_ref, level):
     check(gpu, oracle_ref, items, level, "wave")
 
 
+def test_gpu_long_backward_extensions_on_the_lds_wave_matcher(gpu, oracle_ref):
+    """branch_cases.lds_wave_backward_inputs (the CPU twin: tests/test_emu_wave.py): level 3 with hashLog 14 / chainLog 13 in a small batch is ZJNI_ROUTE_WAVE, whose
+    count_back goes round two, three and four times over these frames"""
+    items = B.lds_wave_backward_inputs()
+    outs = gpu.compress_batch([d for _, d, _ in items], 3, hash_log=14, chain_log=13)
+    assert gpu.lib().zjni_last_route() == 2                        # ZJNI_ROUTE_WAVE
+    for (name, d, _), z in zip(items, outs):
+        assert not isinstance(z, Exception), (name, z)
+        assert z == oracle_ref.compress(d, 3, False, 14, 13), (name, len(z))
+    assert gpu.decompress_batch(outs, [len(d) for _, d, _ in items]) == [d for _, d, _ in items]
+
+
 @pytest.mark.parametrize("need", ("0", "1", "2"))
 def test_gpu_backward_extensions_on_the_lane_pipeline(gpu, oracle_ref, monkeypatch, need):
     """the lane-per-frame match kernels (the run machine at level 3 with flags for no frame, every frame, the picked frames; the lane machine at levels 1 and 2):

@@ -7,6 +7,17 @@ import subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def emu_so(directory, name):
+    """the path of an emulation library: tests/<directory>/<name>, built there by `make` — or the library of the same name in $ZJNI_EMU_LIB_DIR when that holds one
+    (tools/emu_coverage.py: the builds with line counters).  Every loader of an emulation library but emu_lib() below, which has ZJNI_EMU_LIB, goes through here."""
+    d = os.path.join(ROOT, "tests", directory)
+    subprocess.check_call(["make", "-s", "-C", d])
+    over = os.environ.get("ZJNI_EMU_LIB_DIR")
+    if over and os.path.exists(os.path.join(over, name)):
+        return os.path.join(over, name)
+    return os.path.join(d, name)
+
+
 def emu_lib():
     """tests/emu/libzjni_emu.so — lane-serial build of the kernel bodies (test infrastructure)."""
     d = os.path.join(ROOT, "tests", "emu")
@@ -147,7 +158,7 @@ def emu_wave_libs():
     if os.environ.get("ZJNI_EMU_WAVE_LIB"):          # the sanitizer build (tests/test_emu_sanitizer.py)
         names = (os.environ["ZJNI_EMU_WAVE_LIB"],)
     for name in names:
-        L = C.CDLL(os.path.join(d, name))
+        L = C.CDLL(name if os.path.isabs(name) else emu_so("emu", name))
         L.emu_compress_wave.restype = C.c_ulonglong
         L.emu_compress_wave.argtypes = [C.c_char_p, C.c_uint, C.c_char_p, C.c_uint, C.c_uint]
         out.append(L)
